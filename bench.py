@@ -11,9 +11,13 @@ offline) with a decisive, audio-dependent decoder program planted (vlog_amd/weig
 per window, segment boundaries every ~3.5 s), so the north_star parity gates can be checked on the bench's own
 windows (the `parity` block); the JSON reports the actual tokens per window.
 
-The default 1-GPU run appends a `variable` block to the same line: the realistic workload (plant margin_var: each
-window's audio sets its transcript length, so windows end at different steps), 150 windows through the row-set
-decode, timed the same way with its own roofline, decoder steps and active-row fraction (variable_block).
+A plain run does only what the headline figure needs: set up, warm up, time --steps steps, print the line (and with
+--dump-outputs DIR write what the last timed step computed, dump_outputs).  --full adds, outside the timed steps,
+the per-kernel event timing and roofline (one more untimed step, and events on the dominant kernel class in the
+timed ones), the oracle `parity` block on sampled windows of one more step, the CPU baseline, and on 1 GPU a
+`variable` block on the same line: the realistic workload (plant margin_var: each window's audio sets its transcript
+length, so windows end at different steps), 150 windows through the row-set decode, timed the same way with its own
+roofline, decoder steps and active-row fraction (variable_block).
 
 Prints ONE JSON line on rank 0.  `python bench.py` (N=1) or torch.distributed.run --nproc-per-node N.
 """
@@ -90,6 +94,8 @@ class Pipeline:
             self._add_words = functools.partial(WhisperModel.add_word_timestamps, m)
         self.host_group = host_group
         self.keep_windows = ()                  # windows whose encoder output the next step copies to the host
+        self.hold_outputs = False               # True: the next step keeps references to what it computed (--dump-outputs)
+        self.held = None
         self.rank, self.world, self.W, self.beam = rank, world, W, beam
         self.pcm_dev, self.margin_left, self.n_total = pcm_dev, margin_left, n_total
         st = dims.specials
@@ -179,6 +185,8 @@ class Pipeline:
                          crc=crc, gen_stats=gen_stats)
         if self.keep_windows:
             self.kept = dict(res=res, enc={w: enc[w].float().cpu().numpy() for w in self.keep_windows})
+        if self.hold_outputs:
+            self.held = dict(res=res, segs=segs, vtt=vtt, enc=enc, mel=mel)      # references only: nothing is copied
         del enc, mel
 
     def run_stream(self, K: int):
@@ -246,6 +254,7 @@ class Pipeline:
                                 "\"'.。,，!！?？:：”)]}、", 0.0, slots=idx)
             t_al = time.perf_counter() - ta
         n_seg = vtt_bytes = 0
+        all_segs, vtts = [], []
         for k in range(K):
             segs = []
             for w in range(W):
@@ -258,6 +267,8 @@ class Pipeline:
             vtt = generate_webvtt(segs)
             n_seg += len(segs)
             vtt_bytes += len(vtt)
+            all_segs += segs
+            vtts.append(vtt)
         t4 = time.perf_counter()
         for k_, v in (("logmel", t_mel), ("encode", t_enc), ("schedule", 0.0), ("decode", t3 - t2), ("align", t_al),
                       ("host", t4 - t3 - t_al)):
@@ -269,6 +280,9 @@ class Pipeline:
         self.last = dict(tokens=[len(r.tokens) for r in res[:W]], steps=steps / K, segments=n_seg, vtt_bytes=vtt_bytes,
                          crc=crc, gen_stats=gen_stats, stream_batches=K,
                          all_tokens=[len(r.tokens) for r in res])
+        if self.hold_outputs:
+            # every batch's windows (the encoder output and log-mel of a batch are freed before the next one's)
+            self.held = dict(res=res, segs=all_segs, vtt="".join(vtts), enc=None, mel=None)
         return time.perf_counter() - t0
 
 
@@ -471,10 +485,48 @@ def roofline_block(breakdown, prof, dom, args, beam: int = 1, traffic_json: Opti
     return out
 
 
-def timed_run(pipe, eng, steps: int, warmup: int, barrier, profile: bool = True, stream: bool = False):
-    """W untimed warmup steps, one untimed step with every kernel class under events (the breakdown and the
-    dominant single-kernel class), then exactly `steps` timed steps (events on the dominant class only), bracketed
-    by the barrier.  -> (elapsed s, breakdown, timed-region profile, dominant class, stage times of the timed steps)"""
+DUMP_SAMPLE = 1 << 20           # elements kept of each large device array (4 MiB as float32)
+
+
+def dump_outputs(path: str, held: dict, max_length: int = 448) -> dict:
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy (float32 / float64, a few MB in all):
+    every window's tokens (padded with -1) and length, its score / cumulative log-prob / no-speech probability, the
+    segment times behind the WebVTT, the WebVTT bytes, and a fixed seeded sample (the same flat indices in every
+    run) of the two large device arrays on the way, the clamped log-mel and the encoder output.
+    -> {name: shape} of what was written."""
+    os.makedirs(path, exist_ok=True)
+    res = held["res"]
+    tokens = np.full((len(res), max_length), -1.0, np.float32)
+    for i, r in enumerate(res):
+        tokens[i, :len(r.tokens)] = r.tokens[:max_length]
+    arrays = {
+        "tokens": tokens,
+        "token_counts": np.asarray([len(r.tokens) for r in res], np.float32),
+        "scores": np.asarray([[r.score, r.cum_logprob, r.no_speech_prob] for r in res], np.float64).reshape(-1, 3),
+        "segment_times": np.asarray([[s["start"], s["end"]] for s in held["segs"]], np.float64).reshape(-1, 2),
+        "vtt_bytes": np.frombuffer(held["vtt"].encode("utf-8"), np.uint8).astype(np.float32),
+    }
+    for name, seed in (("mel", 1), ("enc", 2)):
+        t = held.get(name)
+        if t is None:
+            continue
+        flat = t.reshape(-1)
+        n = flat.numel()
+        idx = (np.arange(n) if n <= DUMP_SAMPLE else
+               np.sort(np.random.default_rng(seed).integers(0, n, size=DUMP_SAMPLE)))
+        arrays[{"mel": "logmel_sample", "enc": "encoder_output_sample"}[name]] = (
+            flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def timed_run(pipe, eng, steps: int, warmup: int, barrier, profile: bool = True, stream: bool = False,
+              hold_last: bool = False):
+    """W untimed warmup steps, with `profile` one untimed step with every kernel class under events (the breakdown
+    and the dominant single-kernel class), then exactly `steps` timed steps (with `profile`, events on the dominant
+    class only), bracketed by the barrier.  hold_last: the last timed step leaves references to what it computed in
+    pipe.held.  -> (elapsed s, breakdown, timed-region profile, dominant class, stage times of the timed steps)"""
     for _ in range(warmup):
         pipe.step()
     breakdown, dom = None, None
@@ -495,10 +547,13 @@ def timed_run(pipe, eng, steps: int, warmup: int, barrier, profile: bool = True,
         eng.profile(True, classes=[dom])
     t0 = time.perf_counter()
     if stream:
+        pipe.hold_outputs = hold_last
         pipe.run_stream(steps)
     else:
-        for _ in range(steps):
+        for i in range(steps):
+            pipe.hold_outputs = hold_last and i == steps - 1
             pipe.step()
+    pipe.hold_outputs = False
     barrier()
     elapsed = time.perf_counter() - t0
     prof = None
@@ -568,6 +623,13 @@ def main():
                     help="plain random-init weights + planted EOT (round-2 workload) instead of the margin-planted "
                          "model; same kernels and token counts, but near-tied logits (the parity gates cannot hold)")
     ap.add_argument("--check-every", type=int, default=4, help="decode steps between host polls of the live count")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the live per-kernel event timing and roofline, the "
+                         "oracle parity sample, the CPU baseline and the variable-length block (each has its own "
+                         "--no-... switch below).  Without it the run sets up, warms up, times --steps steps and prints "
+                         "the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--traffic-json", default=None, help="PMC traffic summary (default: profiles/traffic_r06_b.json, "
                     "or traffic_r02_fp8.json with --cross-fp8)")
@@ -589,10 +651,12 @@ def main():
     ap.add_argument("--balance", choices=("count", "tokens"), default=None,
                     help="N > 1: windows per GPU by count, or by expected tokens (default for --workload variable)")
     ap.add_argument("--no-variable", action="store_true",
-                    help="skip the variable-length block the default (uniform, 1 GPU) run appends to its line")
+                    help="skip the variable-length block the --full (uniform, 1 GPU) run appends to its line")
     ap.add_argument("--variable-steps", type=int, default=None, help="timed steps of the variable block (default "
                     "max(2, steps // 4))")
     args = ap.parse_args()
+    if not args.full:
+        args.no_profile = args.no_parity = args.no_cpu_baseline = args.no_variable = True
     if args.max_rows is None:
         args.max_rows = 0 if args.workload == "variable" else -1
     if args.balance is None:
@@ -629,7 +693,7 @@ def main():
     dims = model_dims(args.model)
     t = time.perf_counter()
     plant = "margin_var" if args.workload == "variable" else "margin"
-    # the default 1-GPU line also times the variable-length workload (variable_block) on a second engine
+    # with --full the 1-GPU line also times the variable-length workload (variable_block) on a second engine
     run_var = (world == 1 and args.workload == "uniform" and args.beam == 1 and not args.stream and not args.cross_fp8
                and not args.random_weights and not args.no_variable and args.max_rows < 0 and dims.n_dec_layer >= 4)
     base_sd = None
@@ -690,7 +754,13 @@ def main():
             dist.barrier(group=host_group)
 
     elapsed, breakdown, prof, dom, stage_timed = timed_run(pipe, eng, args.steps, args.warmup, barrier,
-                                                           profile=not args.no_profile, stream=args.stream)
+                                                           profile=not args.no_profile, stream=args.stream,
+                                                           hold_last=bool(args.dump_outputs) and rank == 0)
+    dumped = None
+    if pipe.held is not None:
+        dumped = dump_outputs(args.dump_outputs, pipe.held)
+        pipe.held = None
+        log(f"[rank {rank}] outputs of the last timed step written to {args.dump_outputs}: {dumped}")
     rank_info = [[elapsed, W, float(sum(pipe.last.get("all_tokens", pipe.last["tokens"]))), pipe.last["steps"]]]
     if world > 1:
         import torch.distributed as dist
@@ -750,7 +820,10 @@ def main():
                    "weights": (f"synthetic seed 0, random-init + planted eot_after={args.eot_after}" if args.random_weights
                                else f"synthetic seed 0, random-init + margin-planted decoder program (weights.py plant {plant})")},
         "stages_s_per_step": {k: round(v / args.steps, 4) for k, v in stage_timed.items()},
+        "full": args.full,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if world > 1:
         out["ranks"] = [{"elapsed_s": round(r[0], 3), "windows": int(r[1]), "tokens": int(r[2]), "decoder_steps": int(r[3])}
                         for r in rank_info]

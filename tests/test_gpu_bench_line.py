@@ -24,8 +24,9 @@ def _run(*args):
 
 
 def test_bench_line_schema_tiny():
-    d = _run("--model", "tiny", "--windows", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-variable",
-             "--parity-windows", "2")
+    # --full: the roofline and parity blocks checked below are not part of a plain run
+    d = _run("--model", "tiny", "--windows", "8", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
+             "--no-variable", "--parity-windows", "2")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
@@ -41,3 +42,34 @@ def test_bench_line_schema_tiny():
     # no committed PMC file applies to this workload: traffic is null and carries no source label
     assert roof["traffic"] is None and "traffic_source" not in roof
     assert d["parity"]["n"] == 2
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run carries the headline keys and none of the --full blocks; --dump-outputs writes the last timed
+    step's results as float .npy files that agree with the line (token counts, the token CRC)."""
+    import zlib
+
+    import numpy as np
+
+    d = _run("--model", "tiny", "--windows", "8", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 8 * 30.0 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    for k in ("parity", "cpu_baseline", "variable", "kernels_one_step", "encoder_mfma", "decoder_kv_read"):
+        assert k not in d, k
+    arrays = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in sorted(os.listdir(tmp_path))}
+    assert set(arrays) == set(d["dumped_outputs"]) >= {"tokens", "token_counts", "scores", "segment_times",
+                                                        "logmel_sample", "encoder_output_sample"}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+    assert all(np.isfinite(a).all() for a in arrays.values())
+    tokens, counts = arrays["tokens"], arrays["token_counts"].astype(int)
+    assert tokens.shape == (8, 448) and counts.tolist() == [int((row >= 0).sum()) for row in tokens]
+    assert round(float(counts.mean()), 1) == d["config"]["mean_tokens_per_window"]
+    crc = 0
+    for row, n in zip(tokens, counts):
+        crc = zlib.crc32(row[:n].astype(np.int32).tobytes(), crc)
+    assert crc == d["config"]["token_crc32"]
+    assert arrays["scores"].shape == (8, 3) and arrays["segment_times"].shape[1] == 2

@@ -1,11 +1,14 @@
-# rocprofv3 kernel-trace stats of one bench step (env passed through, e.g. VLOG_AMD_XSPLITS=1); TAG names the output
+# rocprofv3 kernel-trace stats of one bench step (env passed through, e.g. VLOG_AMD_XSPLITS=1); TAG names the output,
+# OUT the folder it goes to (default bench_out/ in the repository)
 set -o pipefail
-R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
+R=${REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
+OUT=${OUT:-$R/bench_out}
+mkdir -p $OUT
 TAG=${TAG:-prof}
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$TAG -o run -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $R/gpurun_out/prof_$TAG.log 2>&1 || { tail -20 $R/gpurun_out/prof_$TAG.log; exit 1; }
-F=$(ls $R/gpurun_out/prof_$TAG/*kernel_stats.csv | head -1)
+# --full: the trace also covers the bench's event-profiled step, its parity step and its variable block
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run -- python3 $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > $OUT/prof_$TAG.log 2>&1 || { tail -20 $OUT/prof_$TAG.log; exit 1; }
+F=$(ls $OUT/prof_$TAG/*kernel_stats.csv | head -1)
 python3 - "$F" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
