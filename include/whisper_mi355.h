@@ -222,7 +222,11 @@ int64_t wm_device_bytes(wm_engine* e);
 int32_t wm_profile_classes(void);
 const char* wm_profile_name(int32_t cls);
 int wm_profile(wm_engine* e, int32_t enable);
-/* Engine options (no reference counterpart: scheduling knobs of this build only).
+/* Engine options (no reference counterpart: scheduling knobs of this build only).  The keys below are the rows of
+ * one table in engine.cpp (kOptions) plus the two per-projection forms; any other key fails with "unknown option".
+ * Some have an environment variable (named in that table) that overrides the default at wm_create; its integer
+ * value goes through the same setter as wm_set_option, so a value the setter rejects (VLOG_AMD_DEC_BIG_LDS=100)
+ * makes wm_create fail with the setter's message instead of being clamped.
  *   "cross_mode" (default 1): 1 = factored cross-attention over the encoder output (attn_xenc.hip),
  *   0 = projected cross-KV panels (attn_dec.hip).  Switching re-allocates the window slots (their content is
  *   dropped: call wm_cross_kv again).  The two forms agree to bf16 rounding (not bit-identical).
@@ -261,10 +265,6 @@ int wm_profile(wm_engine* e, int32_t enable);
  *   to the 4-wave route; a split sums its slabs in the residual + LayerNorm combine: f32 rounding).
  *   "decode_gemm_big_lds" (default 72): LDS budget in KiB of the qkv / fc1 / fc2 ring blocks on that route, 72 (two
  *   resident blocks per CU) or 144 (one; the d x d projections always take 144).  Bit-identical either way.
- *   "decode_ln_fold" (default 0; measured slower, kept for A/B): passes of 33..1024 rows whose projections all take the ring route fold each
- *   pre-LayerNorm into its consumer: the residual producer writes bf16(x * gamma) and row sums, the consumer's
- *   epilogue applies rstd * acc - rstd * mean * (W gamma) + (W beta + bias), so no LayerNorm launch follows out and
- *   cout.  Results agree with 0 to the bf16 rounding of a different operand (not bit for bit).
  *   "align_fused" (default 1, process-wide): word alignment's z-score + median filter as one statistics kernel and
  *   one wave-per-row-segment median kernel that recomputes z from the attention (never stored); 0 runs the two-kernel
  *   form that writes z.  Bit-identical.
@@ -276,14 +276,6 @@ int wm_profile(wm_engine* e, int32_t enable);
  *   measured no gain).  Bit-identical.
  *   "cross_attn_snake" (default 0): odd decoder layers walk the factored cross-attention's items in reverse, so
  *   the encoder output read last by one layer is read first by the next (Infinity Cache reuse).  Bit-identical.
- *   "cross_attn_dma" (default 0): 1 = at n_state 1280 with bf16 cross memory, the factored cross-attention streams the
- *   encoder output straight into LDS (LDS-DMA, two tiles ahead); 0 runs the register-staged form.  Bit-identical on
- *   key-split items; measured slower in the bench step.
- *   "cross_attn_chunks" (default 0): 1 = at n_state 1280, greedy passes cut their (window, 32-position tile) units into
- *   one contiguous chunk per CU (stream-K) instead of per-window key splits (the register form runs a chunk's
- *   segments as work items, the LDS-DMA form walks a chunk per workgroup; the two give the same bits); the pieces
- *   of a window are merged like key splits, so results agree with the key-split cut to f32 rounding, not bit for
- *   bit.  Measured slower at the headline's 150 windows.
  *   "cross_attn_blocks" (default 0): grid cap of the cross-attention kernel, which walks its
  *   (window, head, key split) items with a grid stride; 0 launches one block per item.
  *   "cross_attn_fuse" (default 1): bit 0 folds the cq projection's split-K combine into the cross-attention

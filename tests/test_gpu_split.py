@@ -137,3 +137,23 @@ def test_unknown_option_raises(batch):
         eng.set_option("decode_gemm_cols.fc1", 48)
     with pytest.raises(RuntimeError, match="unknown projection"):
         eng.set_option("decode_gemm_cols.nope", 64)
+    # the opt-in forms that were removed went with their keys
+    for gone in ("cross_attn_dma", "cross_attn_chunks", "decode_ln_fold"):
+        with pytest.raises(RuntimeError, match="unknown option"):
+            eng.set_option(gone, 0)
+        with pytest.raises(RuntimeError, match="unknown option"):
+            eng.option(gone)
+
+
+def test_every_documented_option_round_trips(batch):
+    """Every key the header documents reads back, accepts its own value and reads back the same."""
+    from tests.test_option_docs import PER_PROJECTION, PROJECTIONS, header_option_keys
+    _, eng = batch
+    keys = header_option_keys()
+    assert PER_PROJECTION <= keys
+    keys = sorted(keys - PER_PROJECTION) + [k.replace("<proj>", pj) for k in sorted(PER_PROJECTION) for pj in PROJECTIONS]
+    assert len(keys) >= 30
+    for k in keys:
+        v = eng.option(k)
+        eng.set_option(k, v)
+        assert eng.option(k) == v, k

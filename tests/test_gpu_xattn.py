@@ -5,7 +5,9 @@ The two forms are the same arithmetic reassociated (q.(E Wk^T) = (Wk^T q).E, P (
 so they agree to bf16 rounding noise: teacher-forced logits, alignment-head attention and no-speech
 probabilities within the tolerances below, and the same greedy / beam tokens on (almost) every window.  The
 model sizes cover every kernel instantiation: tiny (4 waves x 96 columns), base (8 x 64), small (8 x 96) and,
-without the oracle, large-v3 (8 x 160, the bench configuration)."""
+without the oracle, large-v3 (8 x 160, the bench configuration).  The factored form has one kernel form and one
+cut of a pass (key splits); that slicing a pass into two launches changes no bit is held by
+tests/test_gpu_split.py::test_split_decode_bit_identical."""
 import numpy as np
 import pytest
 import torch
@@ -214,75 +216,3 @@ def test_large_v3_factored_matches_projected():
     assert sum(len(r.tokens) for r in rb) > W * 5
     eng.set_option("cross_mode", 1)
     assert eng.device_bytes() > 0
-
-
-def test_large_v3_dma_form_bit_identical():
-    """The LDS-DMA form of the factored attention (option cross_attn_dma, d = 1280) against the register-staged form
-    (the default), both on key-split items (cross_attn_chunks 0): the same work items, per-wave MFMAs and
-    fixed-order cross-wave sums, so the same bits -- teacher-forced logits over a 40-row prompt (two m-tiles per
-    window), alignment-head capture on the attention kernel (cross_tf 0), greedy and beam-5 decodes (1 and 5 rows per
-    window, rows finishing at different steps).  Then the stream-K chunk cut for greedy passes (opt-in): the
-    register form (a chunk's segments as work items) and the LDS-DMA form (a workgroup walks its chunk) give the
-    same bits; beam and teacher-forced passes are untouched (more than one m-tile per window: items); greedy agrees
-    with the key-split cut to f32 rounding (a window's pieces differ from its key splits); and slicing a pass into
-    two launches (decode_split: 32 greedy rows, two slices of 16) changes no bit."""
-    W, WB = 32, 4                                     # greedy over 32 windows, beam over 4
-    dims, sd, eng, enc = _engine("large-v3", 2, W, eot_after=30)
-    del sd
-    st = dims.specials
-    heads = dims.default_alignment_heads()
-    toks = np.array([[st.sot, st.lang_token("en"), st.transcribe, st.no_timestamps] + list(range(500 + 40 * i, 536 + 40 * i))
-                     for i in range(2)])
-    prompt = [st.sot, st.lang_token("en"), st.transcribe]
-    assert eng.option("cross_attn_dma") == 0 and eng.option("cross_attn_chunks") == 0     # the defaults
-    out = {}
-    try:
-        for form, chunks, split in ((0, 0, 0), (1, 0, 0), (0, 1, 0), (1, 1, 0), (0, 1, 1)):
-            eng.set_option("cross_attn_dma", form)
-            eng.set_option("cross_attn_chunks", chunks)
-            eng.set_option("decode_split", split)
-            eng.set_option("cross_tf", 0)
-            eng.reserve(W, 5 * W)
-            eng.cross_kv(enc, 0)
-            lg, at = eng.forward([3, 1], toks, align_heads=heads)
-            eng.set_option("cross_tf", 1)
-            one = eng.forward(list(range(W)), np.array([[st.sot]] * W))[0].cpu().numpy()   # one row per window
-            g, _ = eng.generate(list(range(W)), [prompt] * W, suppress_tokens=_sup(st), max_length=60)
-            b, _ = eng.generate(list(range(WB)), [prompt] * WB, beam_size=5, patience=1.0, suppress_tokens=_sup(st),
-                                max_length=60)
-            out[(form, chunks, split)] = (lg.cpu().numpy(), at.cpu().numpy(), g, b, one)
-    finally:
-        eng.set_option("cross_attn_dma", 0)
-        eng.set_option("cross_attn_chunks", 0)
-        eng.set_option("decode_split", 0)
-        eng.set_option("cross_tf", 1)
-
-    def same(x, y, greedy=True):
-        if greedy:
-            assert np.array_equal(x[4], y[4]), np.abs(x[4] - y[4]).max()
-        assert np.array_equal(x[0], y[0]), np.abs(x[0] - y[0]).max()
-        assert np.array_equal(x[1], y[1]), np.abs(x[1] - y[1]).max()
-        for ra, rb in (((x[2], y[2]),) if greedy else ()) + ((x[3], y[3]),):
-            assert [r.tokens for r in ra] == [r.tokens for r in rb]
-            assert [r.score for r in ra] == [r.score for r in rb]
-            assert [r.no_speech_prob for r in ra] == [r.no_speech_prob for r in rb]
-
-    reg, items, chunks, dchunks, sliced = (out[(0, 0, 0)], out[(1, 0, 0)], out[(0, 1, 0)], out[(1, 1, 0)],
-                                           out[(0, 1, 1)])
-    assert np.all(np.isfinite(items[0])) and np.allclose(items[1].sum(-1), 1.0, atol=1e-4)
-    same(reg, items)                  # the two forms on key-split items
-    same(chunks, dchunks)             # ... and on the chunk cut (register: segments as items; LDS-DMA: chunk walks)
-    same(items, chunks, greedy=False)
-    same(chunks, sliced)
-    # the chunk cut vs the key splits on the same one-row-per-window pass: f32 rounding of the piece merge, then bf16
-    # activations downstream
-    diff = np.abs(items[4] - chunks[4]).max()
-    assert diff < 0.01 * max(np.abs(items[4]).max(), 1.0), diff
-    for x, y in zip(items[2], chunks[2]):
-        assert abs(x.no_speech_prob - y.no_speech_prob) < 1e-3
-        if x.tokens == y.tokens:
-            assert abs(x.score - y.score) < 2e-3 * max(1.0, abs(x.score)), (x.score, y.score)
-    # random weights: near-tied greedy steps part on rounding noise (test_large_v3_factored_matches_projected); the
-    # records sweeps (test_gpu_logprobs, test_gpu_configs) hold the default cut to the oracle
-    assert sum(x.tokens == y.tokens for x, y in zip(items[2], chunks[2])) >= W // 2
-    assert sum(len(r.tokens) for r in chunks[2]) > W * 5

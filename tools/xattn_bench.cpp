@@ -9,9 +9,8 @@
 #include <vector>
 #include "../vlog_amd/csrc/common.h"
 void launch_xattn(const bf16*, const void*, const float*, const int*, const int*, const int*, int, long long, int, int,
-                  int, int, const XPlan&, int, int, int, int, bf16*, float*, float*, const int*, int, unsigned long long*,
-                  hipStream_t, hipEvent_t, hipEvent_t);
-XPlan xattn_plan(int, int, int, int, int, bool);
+                  int, int, int, int, int, bf16*, float*, float*, const int*, int, unsigned long long*, hipStream_t,
+                  hipEvent_t, hipEvent_t);
 void xattn_set_ablation(int);
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
@@ -57,18 +56,14 @@ int main(int argc, char** argv) {
   const int snake = getenv("XB_SNAKE") ? atoi(getenv("XB_SNAKE")) : 0;
   int launch_no = 0;
   const int keep = getenv("XB_KEEP") ? atoi(getenv("XB_KEEP")) : 0;   // windows loaded with the default policy
-  const int dma = getenv("XB_DMA") ? atoi(getenv("XB_DMA")) : 1;      // bf16: 1 = LDS-DMA form, 0 = register-staged
-  const int sk = getenv("XB_SK") ? atoi(getenv("XB_SK")) : 1;         // LDS-DMA form: 1 = stream-K chunks (ignores splits)
   for (int f8 = 0; f8 < 2; ++f8) {
     if (f8_only >= 0 && f8 != f8_only) continue;
     const double bytes = (double)W * T * d * (f8 ? 1 : 2);
     for (int abl : abls) {
       xattn_set_ablation(abl);
       for (int splits : split_list) {
-        XPlan plan = xattn_plan(W, 1, H, T, d, !f8 && sk && !snake && !keep);
-        if (!plan.sk_W) plan.slabs = splits;
         auto run = [&] {
-          launch_xattn(qp, enc, f8 ? scale : nullptr, slot, rh, nullptr, W, W, 1, H, T, d, plan, snake ? (launch_no++ & 1) : 0, keep, dma, 0, pu, pml,
+          launch_xattn(qp, enc, f8 ? scale : nullptr, slot, rh, nullptr, W, W, 1, H, T, d, splits, snake ? (launch_no++ & 1) : 0, keep, pu, pml,
                        nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr);
         };
         for (int i = 0; i < 3; ++i) run();
@@ -79,8 +74,7 @@ int main(int argc, char** argv) {
         float ms = 0;
         CK(hipEventElapsedTime(&ms, e0, e1));
         const double us = 1000.0 * ms / iters;
-        printf("%s%s%s abl %2d splits %2d  %8.2f us  %7.1f GB/s (encoder output)\n", f8 ? "fp8 " : "bf16",
-               plan.sk_W ? (dma ? " dma chunks" : " chunk items") : !f8 && dma ? " dma" : "", snake ? " snake" : "", abl, plan.sk_W ? plan.sk_P : splits, us,
+        printf("%s%s abl %2d splits %2d  %8.2f us  %7.1f GB/s (encoder output)\n", f8 ? "fp8 " : "bf16", snake ? " snake" : "", abl, splits, us,
                bytes / (us * 1e-6) / 1e9);
       }
     }

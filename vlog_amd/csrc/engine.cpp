@@ -47,14 +47,13 @@ void launch_cross_attn(const bf16*, long long, const bf16*, const bf16*, int, co
 void launch_xpack(const bf16*, bf16*, bf16*, int, int, int, hipStream_t);
 void launch_xq(const bf16*, long long, const CrossFuse&, const bf16*, bf16*, int, int, int, hipStream_t);
 int xattn_splits(int, int, int, int, int);
-XPlan xattn_plan(int, int, int, int, int, bool);
 void launch_xquant8(const bf16*, long long, int, unsigned char*, float*, hipStream_t);
 long long xblock_slot_elems(int T, int d);
 void launch_xblock(const bf16* src, int B, int T, int d, bf16* dst, bool to_blocked, hipStream_t st);
 void launch_xattn(const bf16*, const void*, const float*, const int*, const int*, const int*, int, long long, int, int, int, int,
-                  const XPlan&, int, int, int, int, bf16*, float*, float*, const int*, int, unsigned long long*, hipStream_t, hipEvent_t, hipEvent_t);
-void launch_xcomb_vo(const bf16*, const float*, const XPlan&, int, long long, const bf16*, const float*, const int*, const int*,
-                     bf16*, long long, int, int, int, int, int, float*, const int*, int, hipStream_t);
+                  int, int, int, bf16*, float*, float*, const int*, int, unsigned long long*, hipStream_t, hipEvent_t, hipEvent_t);
+void launch_xcomb_vo(const bf16*, const float*, int, long long, const bf16*, const float*, const int*, const int*,
+                     bf16*, long long, int, int, int, int, float*, const int*, int, hipStream_t);
 
 void launch_token_probs(const float*, int, int, int, const int*, float*, hipStream_t);
 void launch_align_matrix(const float*, int, int, int, int, int, int, int, float*, float*, float*, hipStream_t);
@@ -238,10 +237,6 @@ struct wm_engine {
                              // the 4-wave 64-row groups stay (tools/dec_gemm_bench at 384 rows, profiles/dgb_r06_*).
   int dec_big_fc2_kr = 1280; // ... fc2's K range per block on that plan (0: the whole K; 1280: four ranges, 240 blocks,
                              // slabs summed by its residual + LayerNorm combine; whole K = 60 blocks, 50 us in the step)
-  int dec_ln_fold = 0;       // ring passes (33..1024 rows): LayerNorms folded into their consumers (no combine launch
-                             // after out / cout; fc2's combine writes stats instead of the LayerNorm).  Off: the
-                             // consumers' epilogue costs more than the two launches it removes (dec_gemm 336 vs 319
-                             // ms per step at 150 rows, 656 vs 568 at 750; profiles/ab_r05_ln_fold_v2.txt)
   int dec_big_lds = 72;      // ... qkv / fc1 / fc2 with this LDS budget per ring block (KiB): 72 = two resident blocks
                              // per CU (tools/dec_gemm_bench at 750 rows: qkv 24.7 -> 18.8 us, fc1 31.3 -> 21.4, fc2
                              // 41.6 -> 33.1 against 144; at 256 rows qkv+fc1+fc2 45.6 -> 35.7 us per layer against the
@@ -249,24 +244,12 @@ struct wm_engine {
   int xkeep = 0;             // factored cross-attention: window groups whose encoder output is loaded with the default
                              // cache policy (the rest non-temporal), to keep them in the Infinity Cache across layers
   bool xsnake = false;       // factored cross-attention: odd layers walk each XCD's items in reverse (Infinity Cache reuse)
-  int xdma = 0;              // factored cross-attention, bf16 at n_state 1280: 1 = the LDS-DMA form, 0 = the
-                             // register-staged form (default; same bits on key-split items; attn_xenc.hip).  Headline
-                             // A/B on one box (profiles/ab_r06_xattn_forms.jsonl): register 3773, LDS-DMA chunks 3752,
-                             // LDS-DMA key-split items 3711 RTFx
-  int xchunks = 0;           // ... greedy passes at n_state 1280: 1 = the stream-K chunk cut (register form: its
-                             // segments as items; LDS-DMA form: a chunk per workgroup), 0 = key-split items (default:
-                             // the chunk cut loses at 150 windows, profiles/xattn_bench_r06_chunk_items.txt)
   DevBuf xenc;               // factored: [n_slots][T][d] bf16 encoder outputs (cross_fp8: OCP e4m3 bytes)
   DevBuf xscale;             // cross_fp8: [n_slots][T] f32 per-position scales
   int cross_fp8 = 0;         // opt-in fp8 cross memory (factored form only; changes numerics, never the default)
   DevBuf xwkt;               // factored: Wk^T per layer and head [L][H][d][64] bf16, packed from dec.ckv.w
   DevBuf xwvb;               // factored: Wv per layer and head in 16-column blocks [L][H][d/16][64][16]
   bool xwkt_ready = false;
-  // folded LayerNorm (decode_ln_fold): per decoder layer s = W g and c = W b + bias of qkv (ln1), cq (ln2), fc1 (ln3),
-  // [L][qkv_s 3d | qkv_c 3d | cq_s d | cq_c d | fc1_s 4d | fc1_c 4d] f32, computed once per weight upload
-  DevBuf fold_vec;
-  bool fold_ready = false;
-  DevBuf fold_stat[2];       // producer row sums per decode slice: [d/16][rows][2]
   DevBuf s_qp, s_pu, s_pml;  // factored step scratch: q' [rows][H][d], split partials u/l and (m, l)
   int cross_cap = 0;         // cross-attention grid cap (0: one block per item; >0: persistent grid-stride form,
                              // 2 blocks/CU measured ~2 % faster alone but slower with the fused q combine)
@@ -571,12 +554,6 @@ struct DecSlice {
 
 // Issues decoder layer l for one slice.  `mid` (optional) is recorded on the slice's stream right before its
 // cross-attention, which is where the second slice starts (see decoder_pass).
-// The factored cross-attention may cut a greedy pass into stream-K chunks (attn_xenc.hip xattn_plan): bf16 cross
-// memory, no cache-policy or walk-order experiment on
-static bool xattn_chunks_ok(const wm_engine* e) {
-  return e->xchunks && !e->cross_fp8 && e->xkeep == 0 && !e->xsnake;
-}
-
 void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, const int* row_hyp, const int* done,
                    const int* lin, const std::vector<std::vector<int>>* align_map, int n_align, float* attn,
                    int cross_group, hipEvent_t mid) {
@@ -607,7 +584,7 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
     ProfScope ps(e, P_DEC_GEMM, st, 2.0 * rows * N * K, gemm_bytes(rows, N, K, ob));
     // one window's beam (or a handful of rows): the weight-streaming small-M kernel
     if (sl.total_rows <= 32 && e->dec_gemv && launch_dec_gemv(a, w, ldw, rows, N, K, ep, ws, wsb, st)) return;
-    if (a.lnx || (ep.stat_out && !ep.xg_out)) throw std::runtime_error("decoder: fused LayerNorm operand off the small-M path");
+    if (a.lnx || ep.stat_out) throw std::runtime_error("decoder: fused LayerNorm operand off the small-M path");
     // passes of >= dec_big_rows rows (beam groups of many windows; tools/dec_gemm_bench at 384 and 750 rows): 64-row
     // ring groups; 64 columns for qkv and fc1, and for every projection from 512 rows; fc2's whole K per block
     // (384 rows: 76 vs 86 us per layer for the 150-row plan; 750 rows: 114 vs 159 us)
@@ -653,7 +630,6 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
     if (p > 0 && launch_dec_ring(a, w, ldw, rows, N, K, ep, ws, wsb, kr, st, p, cols, lds, waves)) return;
     if (p == 0 && e->dec_ring && K <= 1280 && sl.total_rows <= 160 && launch_dec_ring(a, w, ldw, rows, N, K, ep, ws, wsb, 0, st))
       return;
-    if (a.fold_stat || ep.xg_out) throw std::runtime_error("decoder: a folded-LayerNorm projection left the ring path");
     launch_gemm(a, w, ldw, rows, N, K, ep, ws, wsb, st);
   };
   // residual-producing GEMMs also apply the LayerNorm that consumes the residual (EPI_RESID_LN: fused into
@@ -684,59 +660,13 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
   // fc2 -> the next layer's ln1 the same way: fc2 (K = 4d) writes the residual and its statistics without split-K,
   // the next layer's qkv normalises its operand (the same for every layer of a pass, so layer l > 0's qkv knows)
   const bool fc2_fuse = ln_fuse && e->dec_gemv_ln_fc2 && gemv_ln_fusable(rows, d, 4 * d, d);
-  // Folded LayerNorms (ring passes): the residual producers (out, cout, fc2) write x, bf16(x * g) into hb and row
-  // sums; the consumers (cq, fc1, next qkv) multiply hb and finish the LayerNorm in their epilogue (gemm.h GemmA
-  // fold_*), so out and cout need no combine launch and fc2's combine writes sums instead of the LayerNorm.  Only
-  // where every projection of the layer takes the ring path with the consumers' whole K per block.
-  const int trows = sl.total_rows;
-  const bool big_route = e->dec_big_rows > 0 && trows >= e->dec_big_rows && trows <= 1024;
-  auto ring_route = [&](int proj, int K) {
-    if (trows <= 32 && e->dec_gemv) return false;
-    if (big_route) return true;
-    const int p = plan_of(proj);
-    return p > 0 || (p == 0 && e->dec_ring && K <= 1280 && trows <= 160);
-  };
-  const bool b128_route = big_route && e->dec_big128 > 0 && trows >= e->dec_big128;   // 8-wave tiles take no fold
-  const bool fold = e->dec_ln_fold && e->fold_ready && !ln_fuse && trows > 32 && trows <= 1024 && !(attn && align_map) && !b128_route &&
-                    ring_route(DEC_QKV, d) && ring_route(DEC_OUT, d) && ring_route(DEC_CQ, d) && ring_route(DEC_COUT, d) &&
-                    ring_route(DEC_FC1, d) && ring_route(DEC_FC2, 4 * d) && e->dec_kr[DEC_QKV] == 0 &&
-                    e->dec_kr[DEC_CQ] == 0 && e->dec_kr[DEC_FC1] == 0 && d % 16 == 0;
-  float* fstat = nullptr;
-  const float* fv = nullptr;
-  if (fold) {
-    DevBuf& fb = e->fold_stat[r0 == 0 ? 0 : 1];
-    fb.ensure((size_t)(d / 16) * rows * 2 * 4);
-    fstat = fb.as<float>();
-    fv = e->fold_vec.as<float>() + (size_t)l * 16 * d;
-  }
-  auto fold_producer = [&](const float* bias, const float* g_next) {
-    GemmEpi ep = epi_of(EPI_RESID_F32, x, d, bias);
-    ep.stat_out = fstat; ep.xg_out = hb; ep.xg_g = g_next; ep.xg_ld = d;
-    return ep;
-  };
-  auto fold_operand = [&](int tiles) {
-    GemmA a = amat(hb, d);
-    a.fold_stat = fstat; a.fold_tiles = tiles; a.fold_rows = rows;
-    return a;
-  };
-  auto fold_epi = [&](GemmEpi ep, size_t off, int N) {
-    ep.bias = nullptr;
-    ep.fold_s = fv + off; ep.fold_c = fv + off + N;
-    return ep;
-  };
-  // fc2's K ranges as the gemm route picks them (the same for every layer of the pass): split-K slabs -> its combine
-  // writes one whole-row tile of sums; one range -> the ring epilogue writes d / 16 tiles (read by the next qkv)
-  const int fc2_kr = e->dec_kr[DEC_FC2] > 0 ? std::min(e->dec_kr[DEC_FC2], 4 * d) : (4 * d <= 1280 || big_route ? 4 * d : 1280);
-  const int fc2_tiles = (4 * d + fc2_kr - 1) / fc2_kr > 1 ? 1 : d / 16;
-  const bool fold_qkv = fold && l > 0;
   bf16* kc = skv + (size_t)(2 * l) * skv_layer;
   bf16* vc = skv + (size_t)(2 * l + 1) * skv_layer;
   {
     GemmEpi ep = epi_of(EPI_DEC_QKV, q, d, W.qkv_b);
     ep.kcache = kc; ep.vcache = vc; ep.row_hyp = row_hyp; ep.row_pos = row_pos;
     ep.d = d; ep.n_head = H; ep.head_dim = 64; ep.n_ctx = C;
-    if (fold_qkv) gemm(DEC_QKV, fold_operand(fc2_tiles), W.qkv_w, d, 3 * d, d, fold_epi(ep, 0, 3 * d));
-    else gemm(DEC_QKV, (fc2_fuse && l > 0) ? ln_operand(W.ln1_w, W.ln1_b) : amat(hb, d), W.qkv_w, d, 3 * d, d, ep);
+    gemm(DEC_QKV, (fc2_fuse && l > 0) ? ln_operand(W.ln1_w, W.ln1_b) : amat(hb, d), W.qkv_w, d, 3 * d, d, ep);
   }
   {
     ProfScope ps(e, P_SELF_ATTN, st, 0, 0, true);
@@ -744,7 +674,7 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
                      sl.total_rows, cross_group);
   }
   gemm(DEC_OUT, amat(ao, d), W.out_w, d, d, d,
-       fold ? fold_producer(W.out_b, W.ln2_w) : ln_fuse ? resid_stat(W.out_b) : resid_ln(W.ln2_w, W.ln2_b, W.out_b));
+       ln_fuse ? resid_stat(W.out_b) : resid_ln(W.ln2_w, W.ln2_b, W.out_b));
   // cq: when the skinny split-K path runs it and no attention is captured, its slabs stay in the scratch and
   // the cross-attention kernel sums them while loading q (no combine launch)
   CrossFuse fz;
@@ -759,8 +689,7 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
       ep.defer_combine = 1;
       fz.q_part = ws; fz.q_splits = sk; fz.q_rows = rows; fz.q_bias = W.cq_b;
     }
-    if (fold) gemm(DEC_CQ, fold_operand(d / 16), W.cq_w, d, d, d, fold_epi(ep, 6 * (size_t)d, d));
-    else gemm(DEC_CQ, ln_fuse ? ln_operand(W.ln2_w, W.ln2_b) : amat(hb, d), W.cq_w, d, d, d, ep);
+    gemm(DEC_CQ, ln_fuse ? ln_operand(W.ln2_w, W.ln2_b) : amat(hb, d), W.cq_w, d, d, d, ep);
   }
   if ((e->cross_fuse & 2) && e->cross_mode == 0) fz.cnt = e->d_cross_cnt.as<int>() + (size_t)r0 * H;
   fz.tf = (attn && align_map && e->cross_tf) ? 1 : 0;
@@ -797,8 +726,7 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
                       n_align, sl.total_rows, e->cross_cap, fz, e->dstat(P_CROSS_ATTN), st, ps.a, ps.b);
   } else if (e->cross_mode == 1) {
     // factored: q' = Wk_h^T q_h, attention over the encoder output, split merge + Wv_h (attn_xenc.hip)
-    const XPlan plan = xattn_plan(sl.total_rows, cross_group, H, T, d, xattn_chunks_ok(e));
-    const int splits = plan.slabs;
+    const int splits = xattn_splits(sl.total_rows, cross_group, H, T, d);
     const size_t prow = (size_t)H * d;
     bf16* qp = e->s_qp.as<bf16>() + (size_t)r0 * prow;
     bf16* pu = e->s_pu.as<bf16>() + (size_t)r0 * 16;         // blocked layout: rows are 16-element records
@@ -813,12 +741,11 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
     {
       ProfScope ps(e, P_CROSS_ATTN, st, 0, 0, true);
       launch_xattn(qp, e->xenc.p, e->cross_fp8 ? e->xscale.as<float>() : nullptr, e->d_hyp_slot.as<int>(), row_hyp, done, rows, sl.total_rows, cross_group, H, T,
-                   d, plan, e->xsnake ? (l & 1) : 0, e->xkeep, e->xdma, r0 / cross_group, pu, pml, probs, hmap, n_align, e->dstat(P_CROSS_ATTN), st, ps.a, ps.b);
+                   d, splits, e->xsnake ? (l & 1) : 0, e->xkeep, pu, pml, probs, hmap, n_align, e->dstat(P_CROSS_ATTN), st, ps.a, ps.b);
     }
     {
       ProfScope ps(e, P_CROSS_COMB, st, 2.0 * rows * d * d, 2.0 * d * d + 2.0 * splits * rows * prow + 2.0 * rows * d);
-      launch_xcomb_vo(pu, pml, plan, r0 / cross_group, sl.total_rows, wv, bv, row_hyp, done, ao, d, rows, cross_group, H, d, T, probs, hmap,
-                      n_align, st);
+      launch_xcomb_vo(pu, pml, splits, sl.total_rows, wv, bv, row_hyp, done, ao, d, rows, H, d, T, probs, hmap, n_align, st);
     }
   } else {
     const size_t po = (size_t)r0 * H * 16;
@@ -830,21 +757,16 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
   }
   if (probs) HIP_OK(hipStreamSynchronize(st));   // the head map buffer is reused by the next layer
   gemm(DEC_COUT, amat(ao, d), W.cout_w, d, d, d,
-       fold ? fold_producer(W.cout_b, W.ln3_w) : ln_fuse ? resid_stat(W.cout_b) : resid_ln(W.ln3_w, W.ln3_b, W.cout_b));
+       ln_fuse ? resid_stat(W.cout_b) : resid_ln(W.ln3_w, W.ln3_b, W.cout_b));
   {
     GemmEpi ep = epi_of(EPI_BF16, ff, 4LL * d, W.fc1_b);
     ep.act = 1;
-    if (fold) gemm(DEC_FC1, fold_operand(d / 16), W.fc1_w, d, 4 * d, d, fold_epi(ep, 8 * (size_t)d, 4 * d));
-    else gemm(DEC_FC1, ln_fuse ? ln_operand(W.ln3_w, W.ln3_b) : amat(hb, d), W.fc1_w, d, 4 * d, d, ep);
+    gemm(DEC_FC1, ln_fuse ? ln_operand(W.ln3_w, W.ln3_b) : amat(hb, d), W.fc1_w, d, 4 * d, d, ep);
   }
   if (l + 1 < L) {
     const auto& Wn = dec_weights(e)[l + 1];
-    if (fold) {
-      gemm(DEC_FC2, amat(ff, 4LL * d), W.fc2_w, 4LL * d, d, 4 * d, fold_producer(W.fc2_b, Wn.ln1_w));
-    } else {
-      gemm(DEC_FC2, amat(ff, 4LL * d), W.fc2_w, 4LL * d, d, 4 * d,
-           fc2_fuse ? resid_stat(W.fc2_b) : resid_ln(Wn.ln1_w, Wn.ln1_b, W.fc2_b));
-    }
+    gemm(DEC_FC2, amat(ff, 4LL * d), W.fc2_w, 4LL * d, d, 4 * d,
+         fc2_fuse ? resid_stat(W.fc2_b) : resid_ln(Wn.ln1_w, Wn.ln1_b, W.fc2_b));
   } else {
     gemm(DEC_FC2, amat(ff, 4LL * d), W.fc2_w, 4LL * d, d, 4 * d, epi_of(EPI_RESID_F32, x, d, W.fc2_b));
   }
@@ -878,7 +800,7 @@ void decoder_pass(wm_engine* e, int rows, const int* row_tok, const int* row_pos
     // per-head Wk^T layout (packed once per upload of dec.ckv.w)
     const int H = m.n_head, T = m.n_audio_ctx;
     const size_t prow = (size_t)H * d;
-    const int splits = xattn_plan(rows, cross_group, H, T, d, xattn_chunks_ok(e)).slabs;
+    const int splits = xattn_splits(rows, cross_group, H, T, d);
     e->s_qp.ensure((size_t)rows * prow * 2);
     e->s_pu.ensure((size_t)splits * rows * prow * 2);
     e->s_pml.ensure((size_t)splits * rows * H * 2 * 4);
@@ -889,18 +811,6 @@ void decoder_pass(wm_engine* e, int rows, const int* row_tok, const int* row_pos
       e->xwkt_ready = true;
     }
     if (!e->xenc.p) throw std::runtime_error("decoder: no encoder slots (wm_reserve + wm_cross_kv first)");
-  }
-  if (e->dec_ln_fold && !e->fold_ready) {
-    const int L2 = m.n_dec_layer;
-    e->fold_vec.ensure((size_t)L2 * 16 * d * 4);
-    for (int l = 0; l < L2; ++l) {
-      const auto& W = dec_weights(e)[l];
-      float* f = e->fold_vec.as<float>() + (size_t)l * 16 * d;
-      launch_fold_vectors(W.qkv_w, 3 * d, d, W.ln1_w, W.ln1_b, W.qkv_b, f, f + 3 * d, st);
-      launch_fold_vectors(W.cq_w, d, d, W.ln2_w, W.ln2_b, W.cq_b, f + 6 * d, f + 7 * d, st);
-      launch_fold_vectors(W.fc1_w, 4 * d, d, W.ln3_w, W.ln3_b, W.fc1_b, f + 8 * d, f + 12 * d, st);
-    }
-    e->fold_ready = true;
   }
   int h0 = (rows / 2 / cross_group) * cross_group;
   const bool split = e->dec_split && logit_rows == nullptr && n_logit == rows && attn == nullptr && h0 >= 16 &&
@@ -2306,6 +2216,101 @@ void require_weights(wm_engine* e) {
   e->weights_ok = true;
 }
 
+// cross_mode / cross_fp8: switching re-allocates the window slots in the new form (their contents are dropped: run
+// wm_cross_kv again)
+void set_cross_form(wm_engine* e, int* field, int v) {
+  if (v == *field) return;
+  HIP_OK(hipDeviceSynchronize());
+  *field = v;
+  const int n = e->n_slots;
+  e->n_slots = 0;
+  if (n > 0) reserve(e, n, e->n_hyp_cap);
+  else { e->ckv.release(); e->xenc.release(); e->xscale.release(); }
+}
+
+void set_dec_plan_preset(wm_engine* e, int64_t v) {
+  if (v != 0 && v != 1) throw std::runtime_error("wm_set_option: decode_gemm_plan is 0 or 1");
+  for (int i = 0; i < DEC_NPROJ; ++i) e->dec_plan[i] = kDecPlanPresets[v][i], e->dec_cols[i] = kDecColsPresets[v][i];
+}
+
+int64_t get_dec_plan_preset(wm_engine* e) {
+  for (int q = 0; q < 2; ++q) {
+    bool eq = true;
+    for (int i = 0; i < DEC_NPROJ; ++i) eq &= e->dec_plan[i] == kDecPlanPresets[q][i] && e->dec_cols[i] == kDecColsPresets[q][i];
+    if (eq) return q;
+  }
+  return -1;                                    // a per-projection setting departs from both presets
+}
+
+int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return std::max(lo, std::min(v, hi)); }
+
+// The scalar engine options, one row each: the wm_set_option / wm_get_option key, the environment variable that
+// overrides the default at wm_create (nullptr: none), a getter and a validating setter.  wm_create passes atoi of
+// every environment variable that is set to the same setter, so a value the setter rejects fails wm_create with
+// the setter's message.  The per-projection forms ("decode_gemm.<proj>", "decode_gemm_cols.<proj>" and the
+// VLOG_AMD_DEC_GEMM / _COLS / _KR lists) are handled beside the table.  include/whisper_mi355.h documents exactly
+// these keys (tests/test_option_docs.py).
+struct OptRow {
+  const char* key;
+  const char* env;
+  int64_t (*get)(wm_engine*);
+  void (*set)(wm_engine*, int64_t);
+};
+#define OPT_GET(expr) [](wm_engine* e) -> int64_t { return expr; }
+#define OPT_SET(stmt) [](wm_engine* e, int64_t v) { stmt; }
+const OptRow kOptions[] = {
+    {"decode_split", "VLOG_AMD_DEC_SPLIT", OPT_GET(e->dec_split), OPT_SET(e->dec_split = v != 0)},
+    {"decode_graph", "VLOG_AMD_DEC_GRAPH", OPT_GET(e->dec_graph), OPT_SET(e->dec_graph = v != 0)},
+    {"decode_gemv", "VLOG_AMD_DEC_GEMV", OPT_GET(e->dec_gemv), OPT_SET(e->dec_gemv = v != 0)},
+    {"decode_gemv_ln", "VLOG_AMD_DEC_GEMV_LN", OPT_GET(e->dec_gemv_ln), OPT_SET(e->dec_gemv_ln = v != 0)},
+    {"decode_gemv_ln_fc2", nullptr, OPT_GET(e->dec_gemv_ln_fc2), OPT_SET(e->dec_gemv_ln_fc2 = v != 0)},
+    {"decode_ring_gemm", "VLOG_AMD_DEC_RING", OPT_GET(e->dec_ring), OPT_SET(e->dec_ring = v != 0)},
+    {"decode_gemm_plan", "VLOG_AMD_DEC_PLAN", get_dec_plan_preset, set_dec_plan_preset},
+    {"decode_gemm_big_rows", "VLOG_AMD_DEC_BIG_ROWS", OPT_GET(e->dec_big_rows),
+     OPT_SET(e->dec_big_rows = (int)clamp64(v, 0, 1 << 20))},
+    {"decode_gemm_big128", "VLOG_AMD_DEC_BIG128", OPT_GET(e->dec_big128), OPT_SET(e->dec_big128 = (int)clamp64(v, 0, 1 << 20))},
+    {"decode_gemm_big_fc2_kr", nullptr, OPT_GET(e->dec_big_fc2_kr),
+     OPT_SET(if (v != 0 && (v < 64 || v % 64 != 0)) throw std::runtime_error("decode_gemm_big_fc2_kr: 0 or a multiple of 64");
+             e->dec_big_fc2_kr = (int)std::min<int64_t>(v, 1 << 20))},
+    {"decode_gemm_big_lds", "VLOG_AMD_DEC_BIG_LDS", OPT_GET(e->dec_big_lds),
+     OPT_SET(if (v != 72 && v != 144) throw std::runtime_error("decode_gemm_big_lds: 72 or 144"); e->dec_big_lds = (int)v)},
+    {"cross_mode", "VLOG_AMD_CROSS_MODE", OPT_GET(e->cross_mode), OPT_SET(set_cross_form(e, &e->cross_mode, v ? 1 : 0))},
+    {"cross_fp8", "VLOG_AMD_CROSS_FP8", OPT_GET(e->cross_fp8), OPT_SET(set_cross_form(e, &e->cross_fp8, v ? 1 : 0))},
+    {"cross_attn_blocks", "VLOG_AMD_CROSS_BLOCKS", OPT_GET(e->cross_cap), OPT_SET(e->cross_cap = (int)clamp64(v, 0, INT32_MAX))},
+    {"cross_attn_fuse", "VLOG_AMD_CROSS_FUSE", OPT_GET(e->cross_fuse), OPT_SET(e->cross_fuse = (int)(v & 3))},
+    {"cross_attn_snake", "VLOG_AMD_XSNAKE", OPT_GET(e->xsnake), OPT_SET(e->xsnake = v != 0)},
+    {"cross_attn_keep", "VLOG_AMD_XKEEP", OPT_GET(e->xkeep), OPT_SET(e->xkeep = (int)clamp64(v, 0, 1 << 20))},
+    {"cross_tf", nullptr, OPT_GET(e->cross_tf), OPT_SET(e->cross_tf = v ? 1 : 0)},
+    {"cross_mfma", nullptr, OPT_GET(e->cross_mfma), OPT_SET(e->cross_mfma = v ? 1 : 0)},
+    {"cross_mfma_fuse", nullptr, OPT_GET(e->cross_mfma_fuse), OPT_SET(e->cross_mfma_fuse = v ? 1 : 0)},
+    {"encode_chunk", "VLOG_AMD_ENC_CHUNK", OPT_GET(e->enc_chunk), OPT_SET(e->enc_chunk = (int)clamp64(v, 1, 4096))},
+    {"gemm_persistent", nullptr, OPT_GET(gemm_8p_get_persistent()), OPT_SET(gemm_8p_set_persistent((int)v))},
+    {"align_fused", nullptr, OPT_GET(align_get_fused()), OPT_SET(align_set_fused((int)v))},
+    {"debug_nan_row", nullptr, OPT_GET(e->dbg_nan_row), OPT_SET(e->dbg_nan_row = (int)clamp64(v, -1, 1 << 30))},
+    {"debug_nan_count", nullptr, OPT_GET(e->dbg_nan_count), OPT_SET(e->dbg_nan_count = (int)clamp64(v, 1, 1 << 20))},
+};
+#undef OPT_GET
+#undef OPT_SET
+
+const OptRow* find_option(const std::string& key) {
+  for (const OptRow& r : kOptions)
+    if (key == r.key) return &r;
+  return nullptr;
+}
+
+// "decode_gemm.<proj>" / "decode_gemm_cols.<proj>": the engine's per-projection entry, or nullptr for any other key
+int* dec_proj_option(wm_engine* e, const std::string& k, const char* who, bool* is_cols) {
+  const bool cols = k.rfind("decode_gemm_cols.", 0) == 0;
+  if (!cols && k.rfind("decode_gemm.", 0) != 0) return nullptr;
+  const std::string pj = k.substr(cols ? 17 : 12);
+  for (int i = 0; i < DEC_NPROJ; ++i)
+    if (pj == kDecProjNames[i]) {
+      *is_cols = cols;
+      return cols ? &e->dec_cols[i] : &e->dec_plan[i];
+    }
+  throw std::runtime_error(std::string(who) + ": unknown projection " + pj);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2329,46 +2334,28 @@ int wm_create(const wm_model_dims* dims, int32_t device, wm_engine** out) {
     auto* e = new wm_engine();
     e->dm = *dims;
     e->device = device;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_SPLIT")) e->dec_split = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_GRAPH")) e->dec_graph = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_GEMV")) e->dec_gemv = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_GEMV_LN")) e->dec_gemv_ln = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_RING")) e->dec_ring = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_LN_FOLD")) e->dec_ln_fold = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_PLAN")) {
-      const int p = std::atoi(v) != 0;
-      for (int i = 0; i < DEC_NPROJ; ++i) e->dec_plan[i] = kDecPlanPresets[p][i], e->dec_cols[i] = kDecColsPresets[p][i];
-    }
-    // per projection, e.g. VLOG_AMD_DEC_GEMM="qkv=32,fc2=64" (rows per block), VLOG_AMD_DEC_COLS="fc1=64"
-    auto per_proj = [](const char* v, int* dst) {
-      std::string spec(v);
-      size_t pos = 0;
-      while (pos < spec.size()) {
-        const size_t end = std::min(spec.find(',', pos), spec.size());
-        const std::string item = spec.substr(pos, end - pos);
-        const size_t eq = item.find('=');
-        if (eq != std::string::npos)
-          for (int i = 0; i < DEC_NPROJ; ++i)
-            if (item.substr(0, eq) == kDecProjNames[i]) dst[i] = std::atoi(item.c_str() + eq + 1);
-        pos = end + 1;
-      }
-    };
-    if (const char* v = std::getenv("VLOG_AMD_DEC_GEMM")) per_proj(v, e->dec_plan);
-    if (const char* v = std::getenv("VLOG_AMD_DEC_COLS")) per_proj(v, e->dec_cols);
-    if (const char* v = std::getenv("VLOG_AMD_DEC_KR")) per_proj(v, e->dec_kr);
-    if (const char* v = std::getenv("VLOG_AMD_CROSS_BLOCKS")) e->cross_cap = std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("VLOG_AMD_CROSS_FUSE")) e->cross_fuse = std::atoi(v) & 3;
-    if (const char* v = std::getenv("VLOG_AMD_ENC_CHUNK")) e->enc_chunk = std::max(1, std::atoi(v));
-    if (const char* v = std::getenv("VLOG_AMD_CROSS_MODE")) e->cross_mode = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_XSNAKE")) e->xsnake = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_XKEEP")) e->xkeep = std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("VLOG_AMD_XDMA")) e->xdma = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_XCHUNKS")) e->xchunks = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_CROSS_FP8")) e->cross_fp8 = std::atoi(v) != 0;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_BIG_LDS")) e->dec_big_lds = std::atoi(v) == 144 ? 144 : 72;
-    if (const char* v = std::getenv("VLOG_AMD_DEC_BIG_ROWS")) e->dec_big_rows = std::max(0, std::atoi(v));
-    if (const char* v = std::getenv("VLOG_AMD_DEC_BIG128")) e->dec_big128 = std::max(0, std::atoi(v));
     try {
+      // environment overrides of the defaults, through the options' own setters (kOptions)
+      for (const OptRow& r : kOptions)
+        if (const char* v = r.env ? std::getenv(r.env) : nullptr) r.set(e, std::atoi(v));
+      // per projection, after the preset: e.g. VLOG_AMD_DEC_GEMM="qkv=32,fc2=64" (rows per block),
+      // VLOG_AMD_DEC_COLS="fc1=64"
+      auto per_proj = [](const char* v, int* dst) {
+        std::string spec(v);
+        size_t pos = 0;
+        while (pos < spec.size()) {
+          const size_t end = std::min(spec.find(',', pos), spec.size());
+          const std::string item = spec.substr(pos, end - pos);
+          const size_t eq = item.find('=');
+          if (eq != std::string::npos)
+            for (int i = 0; i < DEC_NPROJ; ++i)
+              if (item.substr(0, eq) == kDecProjNames[i]) dst[i] = std::atoi(item.c_str() + eq + 1);
+          pos = end + 1;
+        }
+      };
+      if (const char* v = std::getenv("VLOG_AMD_DEC_GEMM")) per_proj(v, e->dec_plan);
+      if (const char* v = std::getenv("VLOG_AMD_DEC_COLS")) per_proj(v, e->dec_cols);
+      if (const char* v = std::getenv("VLOG_AMD_DEC_KR")) per_proj(v, e->dec_kr);
       build_layout(e);
       build_frontend(e, nullptr);
     } catch (...) {
@@ -2419,7 +2406,6 @@ int wm_set_weight(wm_engine* e, const char* name, const void* d_src, int64_t nby
     HIP_OK(hipMemcpyAsync((char*)e->arena.p + it->second.off, d_src, nbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     it->second.set = true;
     if (it->first == "dec.ckv.w") e->xwkt_ready = false;
-    e->fold_ready = false;
   });
 }
 
@@ -2643,82 +2629,16 @@ int wm_set_option(wm_engine* e, const char* key, int64_t value) {
   return guarded(e, [&] {
     if (!key) throw std::runtime_error("wm_set_option: null key");
     const std::string k(key);
-    if (k == "decode_split") e->dec_split = value != 0;
-    else if (k == "decode_graph") e->dec_graph = value != 0;
-    else if (k == "decode_gemv") e->dec_gemv = value != 0;
-    else if (k == "decode_gemv_ln") e->dec_gemv_ln = value != 0;
-    else if (k == "decode_gemv_ln_fc2") e->dec_gemv_ln_fc2 = value != 0;
-    else if (k == "decode_ring_gemm") e->dec_ring = value != 0;
-    else if (k == "decode_gemm_plan") {
-      if (value != 0 && value != 1) throw std::runtime_error("wm_set_option: decode_gemm_plan is 0 or 1");
-      for (int i = 0; i < DEC_NPROJ; ++i) e->dec_plan[i] = kDecPlanPresets[value][i], e->dec_cols[i] = kDecColsPresets[value][i];
-    } else if (k.rfind("decode_gemm.", 0) == 0) {
-      const std::string pj = k.substr(12);
-      int i = 0;
-      while (i < DEC_NPROJ && pj != kDecProjNames[i]) ++i;
-      if (i == DEC_NPROJ) throw std::runtime_error("wm_set_option: unknown projection " + pj);
-      if (value < -2 || value > 160) throw std::runtime_error("wm_set_option: decode_gemm.<proj> in [-2, 160]");
-      e->dec_plan[i] = (int)value;
-    } else if (k.rfind("decode_gemm_cols.", 0) == 0) {
-      const std::string pj = k.substr(17);
-      int i = 0;
-      while (i < DEC_NPROJ && pj != kDecProjNames[i]) ++i;
-      if (i == DEC_NPROJ) throw std::runtime_error("wm_set_option: unknown projection " + pj);
-      if (value != 32 && value != 64) throw std::runtime_error("wm_set_option: decode_gemm_cols.<proj> is 32 or 64");
-      e->dec_cols[i] = (int)value;
+    bool cols = false;
+    if (const OptRow* r = find_option(k)) {
+      r->set(e, value);
+    } else if (int* p = dec_proj_option(e, k, "wm_set_option", &cols)) {
+      if (cols && value != 32 && value != 64) throw std::runtime_error("wm_set_option: decode_gemm_cols.<proj> is 32 or 64");
+      if (!cols && (value < -2 || value > 160)) throw std::runtime_error("wm_set_option: decode_gemm.<proj> in [-2, 160]");
+      *p = (int)value;
+    } else {
+      throw std::runtime_error("wm_set_option: unknown option " + k);
     }
-    else if (k == "cross_attn_blocks") e->cross_cap = (int)std::max<int64_t>(0, value);
-    else if (k == "cross_attn_fuse") e->cross_fuse = (int)(value & 3);
-    else if (k == "cross_attn_snake") e->xsnake = value != 0;
-    else if (k == "cross_attn_keep") e->xkeep = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
-    else if (k == "cross_attn_dma") e->xdma = value != 0;
-    else if (k == "cross_attn_chunks") e->xchunks = value != 0;
-    else if (k == "gemm_persistent") gemm_8p_set_persistent((int)value);
-    else if (k == "align_fused") align_set_fused((int)value);
-    else if (k == "encode_chunk") e->enc_chunk = (int)std::max<int64_t>(1, std::min<int64_t>(value, 4096));
-    else if (k == "cross_fp8") {
-      // fp8 (OCP e4m3) cross memory in the factored form; switching re-allocates the window slots (their
-      // contents are dropped: run wm_cross_kv again)
-      const int v = value ? 1 : 0;
-      if (v != e->cross_fp8) {
-        HIP_OK(hipDeviceSynchronize());
-        e->cross_fp8 = v;
-        const int n = e->n_slots;
-        e->n_slots = 0;
-        if (n > 0) reserve(e, n, e->n_hyp_cap);
-        else { e->xenc.release(); e->xscale.release(); }
-      }
-    }
-    else if (k == "cross_mode") {
-      // switching re-allocates the window slots in the new form (their contents are dropped: run
-      // wm_cross_kv again)
-      const int v = value ? 1 : 0;
-      if (v != e->cross_mode) {
-        HIP_OK(hipDeviceSynchronize());
-        e->cross_mode = v;
-        const int n = e->n_slots;
-        e->n_slots = 0;
-        if (n > 0) reserve(e, n, e->n_hyp_cap);
-        else { e->ckv.release(); e->xenc.release(); }
-      }
-    }
-    else if (k == "debug_nan_row") e->dbg_nan_row = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 30));
-    else if (k == "debug_nan_count") e->dbg_nan_count = (int)std::max<int64_t>(1, std::min<int64_t>(value, 1 << 20));
-    else if (k == "cross_tf") e->cross_tf = value ? 1 : 0;
-    else if (k == "cross_mfma") e->cross_mfma = value ? 1 : 0;
-    else if (k == "cross_mfma_fuse") e->cross_mfma_fuse = value ? 1 : 0;
-    else if (k == "decode_gemm_big_rows") e->dec_big_rows = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
-    else if (k == "decode_gemm_big128") e->dec_big128 = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
-    else if (k == "decode_gemm_big_fc2_kr") {
-      if (value != 0 && (value < 64 || value % 64 != 0)) throw std::runtime_error("decode_gemm_big_fc2_kr: 0 or a multiple of 64");
-      e->dec_big_fc2_kr = (int)std::min<int64_t>(value, 1 << 20);
-    }
-    else if (k == "decode_ln_fold") e->dec_ln_fold = value ? 1 : 0;
-    else if (k == "decode_gemm_big_lds") {
-      if (value != 72 && value != 144) throw std::runtime_error("decode_gemm_big_lds: 72 or 144");
-      e->dec_big_lds = (int)value;
-    }
-    else throw std::runtime_error("wm_set_option: unknown option " + k);
   });
 }
 
@@ -2726,49 +2646,9 @@ int wm_get_option(wm_engine* e, const char* key, int64_t* value) {
   return guarded(e, [&] {
     if (!key || !value) throw std::runtime_error("wm_get_option: null argument");
     const std::string k(key);
-    auto proj = [&](size_t n) {
-      const std::string pj = k.substr(n);
-      for (int i = 0; i < DEC_NPROJ; ++i)
-        if (pj == kDecProjNames[i]) return i;
-      throw std::runtime_error("wm_get_option: unknown projection " + pj);
-    };
-    if (k == "decode_split") *value = e->dec_split;
-    else if (k == "decode_graph") *value = e->dec_graph;
-    else if (k == "decode_gemv") *value = e->dec_gemv;
-    else if (k == "decode_gemv_ln") *value = e->dec_gemv_ln;
-    else if (k == "decode_gemv_ln_fc2") *value = e->dec_gemv_ln_fc2;
-    else if (k == "decode_ring_gemm") *value = e->dec_ring;
-    else if (k == "decode_gemm_plan") {
-      int p = -1;
-      for (int q = 0; q < 2 && p < 0; ++q) {
-        bool eq = true;
-        for (int i = 0; i < DEC_NPROJ; ++i) eq &= e->dec_plan[i] == kDecPlanPresets[q][i] && e->dec_cols[i] == kDecColsPresets[q][i];
-        if (eq) p = q;
-      }
-      *value = p;                               // -1: a per-projection setting departs from both presets
-    } else if (k.rfind("decode_gemm.", 0) == 0) *value = e->dec_plan[proj(12)];
-    else if (k.rfind("decode_gemm_cols.", 0) == 0) *value = e->dec_cols[proj(17)];
-    else if (k == "cross_attn_blocks") *value = e->cross_cap;
-    else if (k == "cross_attn_fuse") *value = e->cross_fuse;
-    else if (k == "cross_attn_snake") *value = e->xsnake;
-    else if (k == "cross_attn_keep") *value = e->xkeep;
-    else if (k == "cross_attn_dma") *value = e->xdma;
-    else if (k == "cross_attn_chunks") *value = e->xchunks;
-    else if (k == "gemm_persistent") *value = gemm_8p_get_persistent();
-    else if (k == "align_fused") *value = align_get_fused();
-    else if (k == "encode_chunk") *value = e->enc_chunk;
-    else if (k == "cross_fp8") *value = e->cross_fp8;
-    else if (k == "cross_mode") *value = e->cross_mode;
-    else if (k == "debug_nan_row") *value = e->dbg_nan_row;
-    else if (k == "debug_nan_count") *value = e->dbg_nan_count;
-    else if (k == "cross_tf") *value = e->cross_tf;
-    else if (k == "cross_mfma") *value = e->cross_mfma;
-    else if (k == "cross_mfma_fuse") *value = e->cross_mfma_fuse;
-    else if (k == "decode_gemm_big_rows") *value = e->dec_big_rows;
-    else if (k == "decode_gemm_big128") *value = e->dec_big128;
-    else if (k == "decode_gemm_big_fc2_kr") *value = e->dec_big_fc2_kr;
-    else if (k == "decode_ln_fold") *value = e->dec_ln_fold;
-    else if (k == "decode_gemm_big_lds") *value = e->dec_big_lds;
+    bool cols = false;
+    if (const OptRow* r = find_option(k)) *value = r->get(e);
+    else if (const int* p = dec_proj_option(e, k, "wm_get_option", &cols)) *value = *p;
     else throw std::runtime_error("wm_get_option: unknown option " + k);
   });
 }

@@ -150,10 +150,6 @@ bool launch_dec_gemm(const GemmA& a, const bf16* w, long long ldw, int M, int N,
   if ((size_t)mf * 16 * KR * 2 > 150 * 1024) return false;      // A panels must fit in LDS
   const bool slab = splitk > 1 || epi.kind == EPI_RESID_LN;
   if (slab && (!ws || (size_t)splitk * M * N * 4 > ws_bytes)) return false;
-  // folded LayerNorm: a consumer needs the stat rows of its pass; a producer writes whole 16-column tiles
-  if (a.fold_stat && (!(a.fold_tiles == 1 || (a.fold_tiles % 2 == 0 && a.fold_tiles <= 80)) || a.fold_rows < M || epi.bias ||
-                      !epi.fold_s || !epi.fold_c || slab)) return false;
-  if (epi.xg_out && (epi.kind != EPI_RESID_F32 || N % 16 != 0 || !epi.stat_out || !epi.bias || !epi.xg_g)) return false;
   switch (epi.kind) {
     case EPI_BF16: dispatch_mf<EPI_BF16>(a, w, ldw, M, N, K, epi, ws, KR, splitk, st); break;
     case EPI_RESID_F32: dispatch_mf<EPI_RESID_F32>(a, w, ldw, M, N, K, epi, ws, KR, splitk, st); break;
@@ -185,25 +181,20 @@ __device__ __forceinline__ void vm_wait(int n) {
   }
 }
 
-// LNF: the folded-LayerNorm consumer (GemmA.fold_*): its row-sum loads are issued before the ring's first panels and
-// reduced after the last one (the epilogue is their only reader), in a separate instantiation so the plain kernel's
-// pipeline is untouched (a runtime-gated prologue made the compiler drain the DMA queue: 1.6x slower at 750 rows).
 // NW = 4 or 8 waves: 2 column halves x NW / 2 row slices.  Eight waves halve each wave's LDS-DMA issue and fragment
 // reads per sub-panel and put two waves on every SIMD, so one wave's DMA issue and barrier wait overlap the other's
 // MFMAs (at 750 rows the 4-wave block was bound by its own per-wave DMA issue, not by the L2).
-template <int MF, int KIND, int R, int PK = 1, int NC = 1, bool LNF = false, int NW = 4>
+template <int MF, int KIND, int R, int PK = 1, int NC = 1, int NW = 4>
 __global__ __launch_bounds__(NW * 64) void dec_ring_kernel(GemmA a, const bf16* __restrict__ w, long long ldw, int M, int N,
                                                            int K, GemmEpi epi, int tiles_n, int splitk, int kr,
                                                            float* __restrict__ part, int rgroups) {
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
-  static_assert(!LNF || NW == 4, "the folded-LayerNorm statistics split assumes 256 threads");
   // a ring slot holds PK consecutive 64-k sub-panels (one barrier per PK x 64 of K); a block covers WR = 32 NC
   // output columns (each wave NC fragments of 16) and ROWS rows (each wave HALF fragments of 16: its row slice)
   constexpr int WRS = NW / 2, ROWS = MF * 16, HALF = MF / WRS, WR = 32 * NC, SUB = (ROWS + WR) * 64, SLOT = PK * SUB,
                 DA = ROWS / (8 * NW), NCW = NC * 4 / NW, DPP = PK * (DA + NCW);
   static_assert(MF % WRS == 0 && ROWS % (8 * NW) == 0 && (NC * 4) % NW == 0, "tile does not split over the waves");
   __shared__ __attribute__((aligned(16))) bf16 smem[R * SLOT];
-  __shared__ float sMR[2][LNF ? ROWS : 1];              // folded LayerNorm: rstd and rstd * mean per row
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
   const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
@@ -214,30 +205,6 @@ __global__ __launch_bounds__(NW * 64) void dec_ring_kernel(GemmA a, const bf16* 
   const int kb = split * kr, klen = min(kr, K - kb), NS = klen / 64, NP = (NS + PK - 1) / PK;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wc = wid & 1, wr = wid >> 1;
-  // folded LayerNorm (a.fold_stat): the row sums [M][tiles][2] of the block's rows are requested BEFORE the ring's
-  // first panels and reduced after them, so their round trip overlaps the DMA latency; 8 threads per row, thread p
-  // summing 16-B pairs of tiles p, p + 8, ... in order, then a fixed xor tree (every block forms the same bits)
-  constexpr int FCH = LNF ? (ROWS + 31) / 32 : 1, FT = LNF ? 10 : 1;  // 32-row chunks; up to 80 tiles = 8 x 10
-  // every load unconditional (clamped address, masked at the reduction): a select on a loaded value made the
-  // compiler wait for it (vmcnt(0)) before the ring's first DMAs
-  float2 fq[FCH][FT];
-  f32x4 pfs[LNF ? NC : 1], pfc[LNF ? NC : 1];
-  if constexpr (LNF) {
-    const int T = a.fold_tiles, part = tid & 7;
-#pragma unroll
-    for (int ch = 0; ch < FCH; ++ch) {
-      const int gr = min(m0 + ch * 32 + (tid >> 3), M - 1);
-      const float* sr = a.fold_stat + (long long)gr * T * 2;
-#pragma unroll
-      for (int j = 0; j < FT; ++j) fq[ch][j] = *(const float2*)(sr + 2 * min(part + 8 * j, T - 1));
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int col0 = min(n0 + (wc * NC + c) * 16 + 4 * (lane >> 4), N - 4);
-      pfs[c] = *(const f32x4*)(epi.fold_s + col0);
-      pfc[c] = *(const f32x4*)(epi.fold_c + col0);
-    }
-  }
   // DMA sources: wave `wid` moves A rows [wid*ROWS/NW, +ROWS/NW) (DA instructions of 8 rows) and W rows
   // [8 NCW wid, +8 NCW) (NCW instructions)
   const bf16* srcA[DA];
@@ -311,32 +278,6 @@ __global__ __launch_bounds__(NW * 64) void dec_ring_kernel(GemmA a, const bf16* 
     }
   }
 
-  if constexpr (LNF) {
-    const int T = a.fold_tiles, part = tid & 7;
-#pragma unroll
-    for (int ch = 0; ch < FCH; ++ch) {
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int j = 0; j < FT; ++j) {
-        const bool in = part + 8 * j < T;
-        s1 += in ? fq[ch][j].x : 0.f;
-        s2 += in ? fq[ch][j].y : 0.f;
-      }
-#pragma unroll
-      for (int o = 1; o < 8; o <<= 1) {
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
-      }
-      const int rr = ch * 32 + (tid >> 3);
-      if ((tid & 7) == 0 && rr < ROWS) {
-        const float mean = s1 / (float)K, var = fmaxf(s2 / (float)K - mean * mean, 0.f);
-        const float rs = rsqrtf(var + 1e-5f);
-        sMR[0][rr] = rs;
-        sMR[1][rr] = rs * mean;
-      }
-    }
-    __syncthreads();
-  }
   const bool to_slab = splitk > 1 || KIND == EPI_RESID_LN;
   // the epilogue's operands (bias chunks; DEC_QKV: each row's hypothesis and position) requested before the first
   // store, at clamped in-bounds addresses (loaded in the fragment loop, each took its own round trip)
@@ -374,44 +315,9 @@ __global__ __launch_bounds__(NW * 64) void dec_ring_kernel(GemmA a, const bf16* 
 #pragma unroll
     for (int i = 0; i < HALF; ++i) {
       const int lr = (wr * HALF + i) * 16 + (lane & 15), row = m0 + lr;
-      // residual producer for a folded LayerNorm (uniform over the block; N % 16 == 0): the updated residual, its
-      // bf16(x * g) operand image and the per-(16-column tile, row) sums, the tile's 4 lanes of a row reduced by a
-      // fixed xor tree (every lane takes part: the 4 lanes of a row share its validity)
-      if (KIND == EPI_RESID_F32 && !to_slab && epi.xg_out) {
-        const bool ok = row < M && col0 < N;
-        f32x4 xn = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ok) {
-          f32x4* px = (f32x4*)((float*)epi.out + (long long)row * epi.ldc + col0);
-          xn = *px + acc[c][i] + *(const f32x4*)(epi.bias + col0);
-          *px = xn;
-          const f32x4 g = *(const f32x4*)(epi.xg_g + col0);
-          bf16x4 xg;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) xg[e] = f2bf(xn[e] * g[e]);
-          *(bf16x4*)(epi.xg_out + (long long)row * epi.xg_ld + col0) = xg;
-        }
-        float s1 = (xn[0] + xn[1]) + (xn[2] + xn[3]);
-        float s2 = (xn[0] * xn[0] + xn[1] * xn[1]) + (xn[2] * xn[2] + xn[3] * xn[3]);
-        s1 += __shfl_xor(s1, 16, 64);
-        s2 += __shfl_xor(s2, 16, 64);
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
-        if (ok && (lane >> 4) == 0)
-          *(float2*)(epi.stat_out + ((long long)row * (N >> 4) + (col0 >> 4)) * 2) = make_float2(s1, s2);
-        continue;
-      }
       if (col0 >= N || row >= M) continue;
       if (to_slab) {
         *(f32x4*)(part + ((long long)split * M + row) * N + col0) = acc[c][i];
-      } else if (LNF) {
-        // folded LayerNorm consumer: rstd (W . gx) - rstd mean (W g) + (W b + bias), then the epilogue kind
-        const float rs = sMR[0][lr], rm = sMR[1][lr];
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaf(acc[c][i][e], rs, pfc[c][e] - rm * pfs[c][e]);
-        if constexpr (PRE) apply_epi4_pre<KIND>(epi, row, col0, v, bpre[c], hpre[KIND == EPI_DEC_QKV ? i : 0],
-                                                ppre[KIND == EPI_DEC_QKV ? i : 0]);
-        else apply_epi4<KIND>(epi, row, col0, v);
       } else {
         if constexpr (PRE) apply_epi4_pre<KIND>(epi, row, col0, acc[c][i], bpre[c], hpre[KIND == EPI_DEC_QKV ? i : 0],
                                                 ppre[KIND == EPI_DEC_QKV ? i : 0]);
@@ -442,7 +348,7 @@ static int ring_lds_kb() {
   return v;
 }
 
-template <int MF, int KIND, int NC, int CAPKB, bool LNF, int NW = 4>
+template <int MF, int KIND, int NC, int CAPKB, int NW = 4>
 static void run_ring_cap_f(const GemmA& a, const bf16* w, long long ldw, int M, int N, int K, const GemmEpi& epi, float* ws,
                          int splitk, int kr, hipStream_t st) {
   constexpr int SUBB = (MF * 16 + 32 * NC) * 128;      // bytes of one 64-k sub-panel
@@ -455,7 +361,7 @@ static void run_ring_cap_f(const GemmA& a, const bf16* w, long long ldw, int M, 
   const int pk = ring_pk();
   if constexpr (R4 >= 3) {
     if (pk == 4) {
-      hipLaunchKernelGGL((dec_ring_kernel<MF, KIND, R4, 4, NC, LNF, NW>), grid, dim3(NW * 64), 0, st, a, w, ldw, M, N, K, epi, tiles_n,
+      hipLaunchKernelGGL((dec_ring_kernel<MF, KIND, R4, 4, NC, NW>), grid, dim3(NW * 64), 0, st, a, w, ldw, M, N, K, epi, tiles_n,
                          splitk, kr, ws, rgroups);
       WM_LAUNCH_CHECK("dec_ring_kernel");
       return;
@@ -463,14 +369,14 @@ static void run_ring_cap_f(const GemmA& a, const bf16* w, long long ldw, int M, 
   }
   if constexpr (R2 >= 3) {
     if (pk >= 2) {
-      hipLaunchKernelGGL((dec_ring_kernel<MF, KIND, R2, 2, NC, LNF, NW>), grid, dim3(NW * 64), 0, st, a, w, ldw, M, N, K, epi, tiles_n,
+      hipLaunchKernelGGL((dec_ring_kernel<MF, KIND, R2, 2, NC, NW>), grid, dim3(NW * 64), 0, st, a, w, ldw, M, N, K, epi, tiles_n,
                          splitk, kr, ws, rgroups);
       WM_LAUNCH_CHECK("dec_ring_kernel");
       return;
     }
   }
   static_assert(R * SUBB <= 160 * 1024, "ring exceeds the LDS");
-  hipLaunchKernelGGL((dec_ring_kernel<MF, KIND, R, 1, NC, LNF, NW>), grid, dim3(NW * 64), 0, st, a, w, ldw, M, N, K, epi, tiles_n, splitk,
+  hipLaunchKernelGGL((dec_ring_kernel<MF, KIND, R, 1, NC, NW>), grid, dim3(NW * 64), 0, st, a, w, ldw, M, N, K, epi, tiles_n, splitk,
                      kr, ws, rgroups);
   WM_LAUNCH_CHECK("dec_ring_kernel");
 }
@@ -479,19 +385,13 @@ template <int MF, int KIND, int NC, int CAPKB>
 static void run_ring_cap(const GemmA& a, const bf16* w, long long ldw, int M, int N, int K, const GemmEpi& epi, float* ws,
                          int splitk, int kr, hipStream_t st, int waves) {
   if constexpr (MF % 4 == 0 && MF * 16 % 64 == 0 && NC % 2 == 0) {
-    if (waves == 8 && !a.fold_stat) {
-      run_ring_cap_f<MF, KIND, NC, CAPKB, false, 8>(a, w, ldw, M, N, K, epi, ws, splitk, kr, st);
+    if (waves == 8) {
+      run_ring_cap_f<MF, KIND, NC, CAPKB, 8>(a, w, ldw, M, N, K, epi, ws, splitk, kr, st);
       return;
     }
   }
-  if (waves == 8) throw std::runtime_error("dec_ring: 8 waves need 64 or 128 rows x 64 or 128 columns, no folded LayerNorm");
-  if constexpr (KIND == EPI_BF16 || KIND == EPI_DEC_QKV) {
-    if (a.fold_stat) {
-      run_ring_cap_f<MF, KIND, NC, CAPKB, true>(a, w, ldw, M, N, K, epi, ws, splitk, kr, st);
-      return;
-    }
-  }
-  run_ring_cap_f<MF, KIND, NC, CAPKB, false>(a, w, ldw, M, N, K, epi, ws, splitk, kr, st);
+  if (waves == 8) throw std::runtime_error("dec_ring: 8 waves need 64 or 128 rows x 64 or 128 columns");
+  run_ring_cap_f<MF, KIND, NC, CAPKB>(a, w, ldw, M, N, K, epi, ws, splitk, kr, st);
 }
 
 template <int MF, int KIND, int NC>
@@ -535,9 +435,9 @@ bool launch_dec_ring(const GemmA& a, const bf16* w, long long ldw, int M, int N,
                      size_t ws_bytes, int kr, hipStream_t st, int rows_per_block, int cols, int lds_kb, int waves) {
   if (lds_kb != 0 && lds_kb != 72 && lds_kb != 144) return false;
   if (waves != 4 && waves != 8) return false;
-  if (waves == 8) {                      // 8 waves: 64 / 128 rows per block x 64 / 128 columns, no folded LayerNorm
+  if (waves == 8) {                      // 8 waves: 64 / 128 rows per block x 64 / 128 columns
     const int rows = rows_per_block > 0 ? std::min(rows_per_block, ((M + 31) / 32) * 32) : M;
-    if (cols < 64 || !(rows > 32 && rows <= 128) || a.fold_stat) return false;
+    if (cols < 64 || !(rows > 32 && rows <= 128)) return false;
   }
   if ((rows_per_block <= 0 && M > 160) || rows_per_block > 160 || N % 4 != 0 || K % 64 != 0) return false;
   if (cols != 32 && cols != 64 && cols != 128) return false;
@@ -549,10 +449,6 @@ bool launch_dec_ring(const GemmA& a, const bf16* w, long long ldw, int M, int N,
   if ((K - (splitk - 1) * kr) % 64 != 0) return false;
   const bool slab = splitk > 1 || epi.kind == EPI_RESID_LN;
   if (slab && (!ws || (size_t)splitk * M * N * 4 > ws_bytes)) return false;
-  // folded LayerNorm: a consumer needs the stat rows of its pass; a producer writes whole 16-column tiles
-  if (a.fold_stat && (!(a.fold_tiles == 1 || (a.fold_tiles % 2 == 0 && a.fold_tiles <= 80)) || a.fold_rows < M || epi.bias ||
-                      !epi.fold_s || !epi.fold_c || slab)) return false;
-  if (epi.xg_out && (epi.kind != EPI_RESID_F32 || N % 16 != 0 || !epi.stat_out || !epi.bias || !epi.xg_g)) return false;
   if (!slab && (epi.ldc % 4 != 0 || (epi.rpb != 0 && epi.bstride % 4 != 0))) return false;
   switch (epi.kind) {
     case EPI_BF16: dispatch_ring<EPI_BF16>(a, w, ldw, M, N, K, epi, ws, splitk, kr, rows_per_block, cols, st, lds_kb, waves); break;
@@ -703,10 +599,6 @@ bool launch_dec_oneshot(const GemmA& a, const bf16* w, long long ldw, int M, int
   const int kr = K / splitk;
   const bool slab = splitk > 1 || epi.kind == EPI_RESID_LN;
   if (slab && (!ws || (size_t)splitk * M * N * 4 > ws_bytes)) return false;
-  // folded LayerNorm: a consumer needs the stat rows of its pass; a producer writes whole 16-column tiles
-  if (a.fold_stat && (!(a.fold_tiles == 1 || (a.fold_tiles % 2 == 0 && a.fold_tiles <= 80)) || a.fold_rows < M || epi.bias ||
-                      !epi.fold_s || !epi.fold_c || slab)) return false;
-  if (epi.xg_out && (epi.kind != EPI_RESID_F32 || N % 16 != 0 || !epi.stat_out || !epi.bias || !epi.xg_g)) return false;
   if (!slab && (epi.ldc % 4 != 0 || (epi.rpb != 0 && epi.bstride % 4 != 0))) return false;
   switch (epi.kind) {
     case EPI_BF16: dispatch_oneshot<EPI_BF16>(a, w, ldw, M, N, K, epi, ws, splitk, kr, nc, st); break;
@@ -1035,10 +927,6 @@ bool launch_dec_gemv(const GemmA& a, const bf16* w, long long ldw, int M, int N,
   }
   const bool slab = splitk > 1 || epi.kind == EPI_RESID_LN;
   if (slab && (!ws || (size_t)splitk * M * N * 4 > ws_bytes)) return false;
-  // folded LayerNorm: a consumer needs the stat rows of its pass; a producer writes whole 16-column tiles
-  if (a.fold_stat && (!(a.fold_tiles == 1 || (a.fold_tiles % 2 == 0 && a.fold_tiles <= 80)) || a.fold_rows < M || epi.bias ||
-                      !epi.fold_s || !epi.fold_c || slab)) return false;
-  if (epi.xg_out && (epi.kind != EPI_RESID_F32 || N % 16 != 0 || !epi.stat_out || !epi.bias || !epi.xg_g)) return false;
   if (!slab && (epi.ldc % 4 != 0 || (epi.rpb != 0 && epi.bstride % 4 != 0))) return false;
   if (a.lnx) {
     if (epi.kind == EPI_DEC_QKV) run_gemv_lna<EPI_DEC_QKV>(a, w, ldw, M, N, K, epi, ws, splitk, kr, st);
@@ -1060,36 +948,4 @@ bool launch_dec_gemv(const GemmA& a, const bf16* w, long long ldw, int M, int N,
   }
   if (slab && !epi.defer_combine) launch_splitk_combine(ws, splitk, M, N, epi, st);
   return true;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Folded-LayerNorm vectors of a consumer projection W [N][K] (bf16, as the GEMM reads it) behind a LayerNorm with
-// affine (g, b): s[n] = sum_k W[n][k] g[k] and c[n] = sum_k W[n][k] b[k] + bias[n], accumulated in f64 in a fixed
-// order (one wave per output column), rounded once to f32.  Run once per weight upload (engine.cpp fold_vectors).
-__global__ __launch_bounds__(256) void fold_vec_kernel(const bf16* __restrict__ w, int N, int K, const float* __restrict__ g,
-                                                       const float* __restrict__ b, const float* __restrict__ bias,
-                                                       float* __restrict__ s_out, float* __restrict__ c_out) {
-  const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (n >= N) return;
-  double s = 0.0, c = 0.0;
-  for (int k = lane; k < K; k += 64) {
-    const double wv = (double)bf2f(w[(long long)n * K + k]);
-    s += wv * (double)g[k];
-    c += wv * (double)b[k];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
-    c += __shfl_xor(c, o, 64);
-  }
-  if (lane == 0) {
-    s_out[n] = (float)s;
-    c_out[n] = (float)(c + (double)bias[n]);
-  }
-}
-
-void launch_fold_vectors(const bf16* w, int N, int K, const float* g, const float* b, const float* bias, float* s_out,
-                         float* c_out, hipStream_t st) {
-  hipLaunchKernelGGL(fold_vec_kernel, dim3((N + 3) / 4), dim3(256), 0, st, w, N, K, g, b, bias, s_out, c_out);
-  WM_LAUNCH_CHECK("fold_vec_kernel");
 }
