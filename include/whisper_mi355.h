@@ -163,6 +163,19 @@ typedef struct wm_generate_args {
   /* Optional statistics [4] (NULL: off): decoder passes, sum over decode passes of the rows in the pass, windows
    * started after the first pass (refills), step graphs captured. */
   int64_t* h_stats;
+  /* ---- ABI 3 (wm_abi_version() >= 3) */
+  /* Two logit rules over each hypothesis' GENERATED tokens (never the prompt, previous text, prefix or hotwords),
+   * applied on the device to the raw logits before every other rule, so they also feed the timestamp forcing and the
+   * log-prob normaliser.  They restate CTranslate2's repetition_penalty / no_repeat_ngram_size of Whisper.generate
+   * [FW↑] from their documented behaviour (parity with CTranslate2 is unpinned: it is not a dependency here).
+   * repetition_penalty p > 0: the logit x of every id already generated becomes x < 0 ? x * p : x / p (timestamps
+   * included); 0 and 1 are off.  no_repeat_ngram_size n >= 1: an id that would complete an n-gram already among the
+   * generated tokens is masked (n = 1: every generated id); 0 is off.  Zero in both fields keeps the ABI 2 behaviour
+   * (a zero-filled struct is valid).  A negative or non-finite penalty, n < 0 or n > max_length fails the call; a
+   * row the rules leave without a legal token fails it as in the failure contract below.  Every decode form applies
+   * them (greedy, sampling, beam, the row-set decodes: a refilled row's history restarts with its new window). */
+  float repetition_penalty;
+  int32_t no_repeat_ngram_size;
 } wm_generate_args;
 /* Failure contract: a NaN / inf logits row or a row whose rules allow no token, detected on the device, fails the
  * call (-1, wm_last_error names the window and step) instead of emitting a token. */

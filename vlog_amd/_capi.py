@@ -11,7 +11,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VLOG_AMD_LIB") or os.path.join(_HERE, "libwhisper_mi355.so")
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 # Every entry point include/whisper_mi355.h declares (tests check the library exports all of them).
 SYMBOLS = (
@@ -42,6 +42,8 @@ class GenerateArgsC(C.Structure):
         # ABI 2
         ("max_rows", C.c_int32), ("compact", C.c_int32), ("h_token_logprobs", C.POINTER(C.c_float)),
         ("h_token_logprobs_other", C.POINTER(C.c_float)), ("h_stats", C.POINTER(C.c_int64)),
+        # ABI 3
+        ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32),
     ]
 
 

@@ -948,6 +948,10 @@ SearchParams search_params(wm_engine* e, const wm_generate_args* a, float* logit
   sp.cum = e->d_cum.as<float>(); sp.row_tok = e->d_row_tok.as<int>(); sp.row_pos = e->d_row_pos.as<int>();
   sp.n_active = e->d_n_active.as<int>(); sp.cand_tok = e->d_cand_tok.as<int>(); sp.cand_lp = e->d_cand_lp.as<float>();
   sp.err = e->d_n_active.as<int>() + 1;
+  // 0 in either field is "off" (a zero-filled ABI 2 struct); validated in generate.  The values are baked into a
+  // captured step graph, which is safe: every StepGraph lives inside one wm_generate call and is never reused.
+  sp.rep_penalty = a->repetition_penalty == 0.f ? 1.0f : a->repetition_penalty;
+  sp.no_repeat_ngram = a->no_repeat_ngram_size;
   return sp;
 }
 
@@ -1018,6 +1022,10 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   if (W <= 0) return;
   if (P <= 0 || P >= a->max_length || a->max_length > C) throw std::runtime_error("generate: bad prompt_len/max_length");
   if (a->sot_index >= P) throw std::runtime_error("generate: sot_index outside the prompt");
+  if (!(a->repetition_penalty >= 0.f) || std::isinf(a->repetition_penalty))
+    throw std::runtime_error("generate: repetition_penalty must be a finite value > 0 (0 or 1: off)");
+  if (a->no_repeat_ngram_size < 0 || a->no_repeat_ngram_size > a->max_length)
+    throw std::runtime_error("generate: no_repeat_ngram_size must be in [0, max_length] (0: off)");
   const bool beam = a->beam_size > 1 && a->temperature <= 0.f;
   const bool sampling = a->temperature > 0.f;
   const int per = beam ? a->beam_size : (sampling ? std::max(1, a->num_hypotheses) : 1);
@@ -2316,7 +2324,7 @@ int* dec_proj_option(wm_engine* e, const std::string& k, const char* who, bool* 
 extern "C" {
 
 const char* wm_last_error(void) { return g_err.c_str(); }
-int32_t wm_abi_version(void) { return 2; }
+int32_t wm_abi_version(void) { return 3; }
 
 int wm_create(const wm_model_dims* dims, int32_t device, wm_engine** out) {
   try {

@@ -47,6 +47,10 @@ struct SearchParams {
   int* res_tok; int* res_len; float* res_cum;   // [n_out][n_ctx] generated tokens (no prompt), [n_out], [n_out]
   float* res_lp;                   // [n_out][n_ctx] per-step records (with tok_lp; nullptr: none)
   float* res_lp_other;
+  // rules over the hypothesis' generated tokens (search.hip header): penalty 1 and n-gram size 0 are off, and
+  // launch_logits_select then runs the instantiations without them
+  float rep_penalty;               // > 0
+  int no_repeat_ngram;             // >= 0
 };
 
 struct BeamParams {

@@ -10,6 +10,15 @@
 // segment log-sum-exps without a third pass.  Greedy and sampling (Gumbel-max over logits / T) update the
 // sequence state in the same kernel; beam search emits each hypothesis's top beam+1 candidates and a
 // per-window kernel ranks them (openai BeamSearchDecoder semantics, patience, finished list).
+//
+// Two optional rules act on the raw logits BEFORE all of the above (so they also feed the timestamp forcing and the
+// normaliser), restating CTranslate2's RepetitionPenalty and NoRepeatNgram logit processors from their documented
+// behaviour; CTranslate2 is not a dependency of this project, so parity with it is unpinned like the rest of
+// DESIGN.md §4 (the pinned reference is tests/repetition_ref.py, checked against transformers' processors).  Both
+// are defined over the hypothesis' GENERATED tokens seq[sample_begin : len] only (never the prompt):
+//   repetition penalty p: every id in that history gets x < 0 ? x * p : x / p (timestamps included);
+//   no-repeat n-gram n: every id that would complete an n-gram already in that history is masked.
+// They live in their own instantiations (RULES): with both off the kernels launched are the ones without them.
 #include "search.h"
 #include <stdexcept>
 #include <string>
@@ -67,8 +76,14 @@ __device__ float block_sum(float v, float* sh) {
 // the registers its mode needs next to the register-resident row.
 // REC: also write the per-step records (p.tok_lp / p.tok_lp_other; an extra register pass for the best other
 // token), instantiated only when a caller asks for them.
-template <int MODE, bool REC>
+// RULES: the repetition penalty / no-repeat n-gram rules (header comment).  Two LDS tables in the suppress_bits
+// layout (id t -> word t % SB, bit t / SB) are filled by the history scan that already finds the last timestamp:
+// s_seen marks the ids of the generated history, s_ban the ids an n-gram repeat would complete.  Each thread then
+// reads its own two words once: the ban word joins `rule`, the seen word rescales the register-resident row.
+template <int MODE, bool REC, bool RULES>
 __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
+  __shared__ unsigned long long s_seen[RULES ? SB : 1];
+  __shared__ unsigned long long s_ban[RULES ? SB : 1];
   __shared__ Cand sh_c[NW];
   __shared__ float sh_f[NW];
   __shared__ int s_info[4];
@@ -83,9 +98,29 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
   // position of the last sampled timestamp: a block-wide max instead of a serial backward scan (a text-only
   // history made thread 0 walk the whole sequence one dependent load at a time)
   if (tid == 0) s_last_ts = -1;
+  if (RULES) {
+    s_seen[tid] = 0;
+    s_ban[tid] = 0;
+  }
   __syncthreads();
-  for (int i = p.sample_begin + tid; i < len; i += SB)
-    if (seq[i] >= tb) atomicMax(&s_last_ts, i);
+  for (int i = p.sample_begin + tid; i < len; i += SB) {
+    const int t = seq[i];
+    if (t >= tb) atomicMax(&s_last_ts, i);
+    if (RULES && t >= 0 && t < SB * 64) {
+      const int w = 2 * (t % SB) + ((t / SB) >> 5);        // 32-bit half of the id's 64-bit word
+      const unsigned bit = 1u << ((t / SB) & 31);
+      if (p.rep_penalty != 1.0f) atomicOr((unsigned*)s_seen + w, bit);
+      // seq[i] ends an n-gram of the history whose first n-1 tokens are the last n-1 generated: it may not follow them
+      // again.  j = this token's index among the generated ones: its n-gram starts at j - (n-1) >= 0 (so the history
+      // holds >= n tokens and every index below stays inside it).  n = 1 compares nothing: every generated id is banned.
+      const int n = p.no_repeat_ngram, j = i - p.sample_begin;
+      if (n > 0 && j >= n - 1) {
+        bool same = true;
+        for (int m = 1; m < n && same; ++m) same = seq[i - m] == seq[len - m];
+        if (same) atomicOr((unsigned*)s_ban + w, bit);
+      }
+    }
+  }
   __syncthreads();
   if (tid == 0) {
     const int ns = len - p.sample_begin;
@@ -145,6 +180,14 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
 #pragma unroll
     for (int k = 0; k < PER; ++k)
       xv[RES ? k : 0] = *(const float*)((const char*)lg + (unsigned)(min(tid + k * SB, V - 1) * 4));
+  }
+  if (RULES) {
+    rule |= s_ban[tid];
+    const unsigned long long seen = s_seen[tid];
+    const float pen = p.rep_penalty, inv_pen = 1.0f / pen;
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if ((seen >> k) & 1) xv[k] *= xv[k] < 0.f ? pen : inv_pen;
   }
   live = ~(sup | rule) & ((1ull << PER) - 1);
   // pass 1: per-segment max / argmax (and Gumbel keys for sampling, local top-k for beam)
@@ -394,7 +437,15 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
   }
   __shared__ int s_fin;
   if (tid == 0) {
-    const float lp = lg[tok] - Z;
+    // (the row's registers belong to another thread: re-read the logit and, RULES, penalise it exactly as above)
+    float lp;
+    if constexpr (RULES) {
+      float xt = lg[tok];
+      if ((s_seen[tok % SB] >> (tok / SB)) & 1) xt *= xt < 0.f ? p.rep_penalty : 1.0f / p.rep_penalty;
+      lp = xt - Z;
+    } else {
+      lp = lg[tok] - Z;
+    }
     const float cum = p.cum[h] + lp;
     p.cum[h] = cum;
     if (REC && p.tok_lp) {
@@ -462,13 +513,21 @@ void launch_logits_select(const SearchParams& p, int n_rows, hipStream_t st) {
   if (p.res_tok && (!p.hyp_out || !p.res_len || !p.res_cum || p.mode == 1))
     throw std::runtime_error("logits_select: incomplete output tables");
   const bool rec = p.tok_lp != nullptr && p.mode != 1;     // beam: beam_select_kernel keeps the records
+  if (!(p.rep_penalty > 0.f) || p.no_repeat_ngram < 0)
+    throw std::runtime_error("logits_select: repetition penalty must be > 0 and the n-gram size >= 0");
+  const bool rules = p.rep_penalty != 1.0f || p.no_repeat_ngram > 0;
   const dim3 g(n_rows), b(SB);
-  switch (p.mode * 2 + (rec ? 1 : 0)) {
-    case 0: hipLaunchKernelGGL((logits_select_kernel<0, false>), g, b, 0, st, p); break;
-    case 1: hipLaunchKernelGGL((logits_select_kernel<0, true>), g, b, 0, st, p); break;
-    case 2: case 3: hipLaunchKernelGGL((logits_select_kernel<1, false>), g, b, 0, st, p); break;
-    case 4: hipLaunchKernelGGL((logits_select_kernel<2, false>), g, b, 0, st, p); break;
-    default: hipLaunchKernelGGL((logits_select_kernel<2, true>), g, b, 0, st, p); break;
+  switch ((rules ? 6 : 0) + p.mode * 2 + (rec ? 1 : 0)) {
+    case 0: hipLaunchKernelGGL((logits_select_kernel<0, false, false>), g, b, 0, st, p); break;
+    case 1: hipLaunchKernelGGL((logits_select_kernel<0, true, false>), g, b, 0, st, p); break;
+    case 2: case 3: hipLaunchKernelGGL((logits_select_kernel<1, false, false>), g, b, 0, st, p); break;
+    case 4: hipLaunchKernelGGL((logits_select_kernel<2, false, false>), g, b, 0, st, p); break;
+    case 5: hipLaunchKernelGGL((logits_select_kernel<2, true, false>), g, b, 0, st, p); break;
+    case 6: hipLaunchKernelGGL((logits_select_kernel<0, false, true>), g, b, 0, st, p); break;
+    case 7: hipLaunchKernelGGL((logits_select_kernel<0, true, true>), g, b, 0, st, p); break;
+    case 8: case 9: hipLaunchKernelGGL((logits_select_kernel<1, false, true>), g, b, 0, st, p); break;
+    case 10: hipLaunchKernelGGL((logits_select_kernel<2, false, true>), g, b, 0, st, p); break;
+    default: hipLaunchKernelGGL((logits_select_kernel<2, true, true>), g, b, 0, st, p); break;
   }
   WM_LAUNCH_CHECK("logits_select_kernel");
 }

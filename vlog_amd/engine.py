@@ -297,11 +297,14 @@ class GpuEngine:
                  suppress_tokens: Sequence[int] = (), suppress_blank: bool = True,
                  max_initial_timestamp_index: Optional[int] = 50, with_timestamps: bool = True,
                  sot_index: Optional[int] = None, check_every: int = 4, max_rows: int = 0, compact: bool = False,
-                 record_logprobs: bool = False, stats: Optional[dict] = None) -> Tuple[List[GenResult], int]:
+                 record_logprobs: bool = False, stats: Optional[dict] = None, repetition_penalty: float = 1.0,
+                 no_repeat_ngram_size: int = 0) -> Tuple[List[GenResult], int]:
         """ctranslate2 Whisper.generate over windows in slots (wm_generate).  max_rows / compact: the row-set decode
         (greedy / one sampled hypothesis; windows refill finished rows in the given order, include/whisper_mi355.h);
         beam search with compact drops finished windows' hypotheses from the passes.
-        record_logprobs: per-step log-prob records in each GenResult.  stats: filled with the decode's counters."""
+        record_logprobs: per-step log-prob records in each GenResult.  stats: filled with the decode's counters.
+        repetition_penalty / no_repeat_ngram_size: CTranslate2's two logit rules over each hypothesis' generated tokens,
+        applied on the device before every other rule (1.0 and 0: off; a negative value raises RuntimeError)."""
         W = len(slots)
         P = len(prompts[0])
         if any(len(p) != P for p in prompts):
@@ -329,7 +332,8 @@ class GpuEngine:
             -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index), int(bool(with_timestamps)),
             check_every, _i32p(toks), _i32p(lens), _f32p(scores), _f32p(cum), _f32p(ns), _i32p(steps),
             int(max_rows), int(bool(compact)), _f32p(lp) if lp is not None else None,
-            _f32p(lpo) if lpo is not None else None, st64.ctypes.data_as(C.POINTER(C.c_int64)))
+            _f32p(lpo) if lpo is not None else None, st64.ctypes.data_as(C.POINTER(C.c_int64)),
+            float(repetition_penalty), int(no_repeat_ngram_size))
         with torch.cuda.device(self.device):
             _capi.check(self.lib.wm_generate(self.h, C.byref(a), self.stream_ptr()), "wm_generate")
         res = []

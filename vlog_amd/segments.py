@@ -4,6 +4,7 @@
       timestamp pairs; start/end = window offset + (token - timestamp_begin) * 0.02 s; a single trailing
       timestamp means "no speech after it" (seek advances a whole window), otherwise seek moves to the last
       timestamp (2 mel frames per timestamp step).
+  build_prompt — `get_prompt`: previous text, hotwords, sot sequence and prefix into one decoder prompt.
   compression_ratio — len(utf8) / len(zlib(utf8)) (fallback trigger above 2.4).
   needs_fallback — the generate_with_fallback decision (compression ratio, avg logprob, silence exemption).
   avg_logprob — recovered from the CTranslate2 score: score * len**length_penalty / (len + 1).
@@ -11,7 +12,7 @@
 from __future__ import annotations
 
 import zlib
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 TIME_PRECISION = 0.02
 INPUT_STRIDE = 2
@@ -48,6 +49,42 @@ def split_segments_by_timestamps(tokens: Sequence[int], timestamp_begin: int, ti
         segs.append(dict(seek=seek, start=time_offset, end=time_offset + duration, tokens=tokens))
         seek += segment_size
     return segs, seek, single_ending
+
+
+def build_prompt(encode: Callable[[str], List[int]], sot_sequence: Sequence[int], sot_prev: int, no_timestamps: int,
+                 timestamp_begin: int, max_length: int, previous_tokens: Sequence[int] = (),
+                 without_timestamps: bool = False, prefix: Optional[str] = None,
+                 hotwords: Optional[str] = None) -> List[int]:
+    """faster-whisper 1.1 `WhisperModel.get_prompt`, as a pure function of the tokenizer's ids and `encode`:
+
+      [sot_prev, hotwords (only without a prefix), previous text]  — each cut to max_length // 2 - 1 tokens (the
+          hotwords keep their head, the previous text its tail); the block is there when either part is
+      sot_sequence, then no_timestamps when `without_timestamps`
+      [timestamp_begin (with timestamps on), prefix]               — when a prefix is given
+    """
+    half = max_length // 2
+    previous_tokens = list(previous_tokens)
+    prompt: List[int] = []
+    if previous_tokens or (hotwords and not prefix):
+        prompt.append(sot_prev)
+        if hotwords and not prefix:
+            hw = list(encode(" " + hotwords.strip()))
+            if len(hw) >= half:
+                hw = hw[: half - 1]
+            prompt.extend(hw)
+        if previous_tokens:
+            prompt.extend(previous_tokens[-(half - 1):])
+    prompt.extend(sot_sequence)
+    if without_timestamps:
+        prompt.append(no_timestamps)
+    if prefix:
+        pf = list(encode(" " + prefix.strip()))
+        if len(pf) >= half:
+            pf = pf[: half - 1]
+        if not without_timestamps:
+            prompt.append(timestamp_begin)
+        prompt.extend(pf)
+    return prompt
 
 
 def compression_ratio(text: str) -> float:

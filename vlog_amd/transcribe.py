@@ -293,8 +293,7 @@ class WhisperModel:
                    clip_timestamps: Union[str, List[float]] = "0", hallucination_silence_threshold: Optional[float] = None,
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
                    language_detection_segments: int = 1):
-        for name, val, default in (("repetition_penalty", repetition_penalty, 1), ("no_repeat_ngram_size", no_repeat_ngram_size, 0),
-                                   ("prefix", prefix, None), ("hotwords", hotwords, None), ("multilingual", multilingual, False),
+        for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
             if val != default:
                 raise NotImplementedError(f"{name}={val!r} is not supported by the MI355X engine")
@@ -311,7 +310,8 @@ class WhisperModel:
                 raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
             return self._pipeline().transcribe(
                 audio, language=language, task=task, beam_size=beam_size, best_of=best_of, patience=patience,
-                length_penalty=length_penalty, temperature=temperature,
+                length_penalty=length_penalty, repetition_penalty=repetition_penalty,
+                no_repeat_ngram_size=no_repeat_ngram_size, hotwords=hotwords, temperature=temperature,
                 compression_ratio_threshold=compression_ratio_threshold, log_prob_threshold=log_prob_threshold,
                 no_speech_threshold=no_speech_threshold, suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
                 without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
@@ -373,15 +373,11 @@ class WhisperModel:
         return gen, info
 
     # ------------------------------------------------------------------ prompt / generate
-    def get_prompt(self, tokenizer: Tokenizer, previous_tokens: List[int], without_timestamps: bool = False) -> List[int]:
-        prompt: List[int] = []
-        if previous_tokens:
-            prompt.append(tokenizer.sot_prev)
-            prompt.extend(previous_tokens[-(self.max_length // 2 - 1):])
-        prompt.extend(tokenizer.sot_sequence)
-        if without_timestamps:
-            prompt.append(tokenizer.no_timestamps)
-        return prompt
+    def get_prompt(self, tokenizer: Tokenizer, previous_tokens: List[int], without_timestamps: bool = False,
+                   prefix: Optional[str] = None, hotwords: Optional[str] = None) -> List[int]:
+        return segs.build_prompt(tokenizer.encode, tokenizer.sot_sequence, tokenizer.sot_prev, tokenizer.no_timestamps,
+                                 tokenizer.timestamp_begin, self.max_length, previous_tokens, without_timestamps,
+                                 prefix, hotwords)
 
     def _generate(self, prompt: List[int], options: TranscriptionOptions, temperature: float, max_length: int,
                   seed: int) -> _GenOut:
@@ -394,7 +390,8 @@ class WhisperModel:
             num_hypotheses=options.best_of if sampling else 1, seed=seed, suppress_tokens=options.suppress_tokens,
             suppress_blank=options.suppress_blank, max_initial_timestamp_index=mit,
             with_timestamps=not options.without_timestamps,
-            sot_index=prompt.index(st.sot) if st.sot in prompt else -1, check_every=4)
+            sot_index=prompt.index(st.sot) if st.sot in prompt else -1, check_every=4,
+            repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size)
         r = res[0]
         return _GenOut(r.tokens, r.score, r.no_speech_prob)
 
@@ -474,7 +471,8 @@ class WhisperModel:
             with self._lock:
                 self._use_cross_form(options.beam_size)
                 self._encode(features, seek, segment_size, 0)
-                prompt = self.get_prompt(tokenizer, previous_tokens, options.without_timestamps)
+                prompt = self.get_prompt(tokenizer, previous_tokens, options.without_timestamps,
+                                         prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
                 result, avg_lp, temperature, cr = self.generate_with_fallback(prompt, tokenizer, options, seed=window)
                 skip = segs.should_skip_window(result.no_speech_prob, avg_lp, options.no_speech_threshold,
                                                options.log_prob_threshold)
@@ -725,11 +723,14 @@ class BatchedInferencePipeline:
         m = self.model
         eng = m.engine
         st = m.dims.specials
-        prompt = list(tokenizer.sot_sequence) + ([tokenizer.no_timestamps] if options.without_timestamps else [])
+        if options.prefix is not None:
+            raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
+        ip: List[int] = []
         if options.initial_prompt:
             ip = (tokenizer.encode(" " + options.initial_prompt.strip()) if isinstance(options.initial_prompt, str)
                   else list(options.initial_prompt))
-            prompt = [tokenizer.sot_prev] + ip[-(m.max_length // 2 - 1):] + prompt
+        # one prompt for every window (wm_generate takes one prompt length): hotwords fit, a prefix does not
+        prompt = m.get_prompt(tokenizer, ip, options.without_timestamps, hotwords=options.hotwords)
         max_length = min(m.max_length, len(prompt) + options.max_new_tokens) if options.max_new_tokens else m.max_length
         mit = int(round(options.max_initial_timestamp / m.time_precision))
         per = max(options.beam_size, options.best_of, 1)
@@ -775,7 +776,9 @@ class BatchedInferencePipeline:
                         temperature=T, num_hypotheses=options.best_of if sampling else 1, seed=seed + 7919 * ti + b0,
                         suppress_tokens=options.suppress_tokens, suppress_blank=options.suppress_blank,
                         max_initial_timestamp_index=mit, with_timestamps=not options.without_timestamps,
-                        sot_index=prompt.index(st.sot), check_every=4, compact=self.compact)
+                        sot_index=prompt.index(st.sot), check_every=4, compact=self.compact,
+                        repetition_penalty=options.repetition_penalty,
+                        no_repeat_ngram_size=options.no_repeat_ngram_size)
                     still = []
                     for i, r in zip(pending, res):
                         alp = segs.avg_logprob(r.score, len(r.tokens), options.length_penalty)
@@ -842,16 +845,18 @@ class BatchedInferencePipeline:
                    hallucination_silence_threshold: Optional[float] = None, batch_size: int = 16,
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
                    language_detection_segments: int = 1):
-        for name, val, default in (("repetition_penalty", repetition_penalty, 1), ("no_repeat_ngram_size", no_repeat_ngram_size, 0),
-                                   ("prefix", prefix, None), ("hotwords", hotwords, None), ("multilingual", multilingual, False),
+        for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
             if val != default:
                 raise NotImplementedError(f"{name}={val!r} is not supported by the MI355X engine")
+        if prefix is not None:       # every window of a batch shares one prompt length; a prefix belongs to the first only
+            raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
         prep = self._prepare(audio, language, vad_filter, vad_parameters, language_detection_segments,
                              language_detection_threshold)
         tokenizer = self.model.tokenizer(task=task, language=prep["language"])
         options = self._options(
             tokenizer, beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
+            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, hotwords=hotwords,
             temperature=temperature, compression_ratio_threshold=compression_ratio_threshold,
             log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
             initial_prompt=initial_prompt, suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
@@ -875,6 +880,8 @@ class BatchedInferencePipeline:
         Returns [(segments, info)] per file, in input order; each file's result is what `transcribe` gives for
         it alone (same windows, prompts and options)."""
         n = len(audios)
+        if kw.pop("prefix", None) is not None:
+            raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
         langs = list(language) if isinstance(language, (list, tuple)) else [language] * n
         if len(langs) != n:
             raise ValueError("one language per file")
@@ -952,11 +959,12 @@ class BatchedInferencePipeline:
                  suppress_tokens: Optional[List[int]] = [-1], without_timestamps: bool = True,
                  max_initial_timestamp: float = 1.0, word_timestamps: bool = False,
                  prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
-                 max_new_tokens: Optional[int] = None, clip_timestamps=None) -> TranscriptionOptions:
+                 max_new_tokens: Optional[int] = None, clip_timestamps=None, repetition_penalty: float = 1,
+                 no_repeat_ngram_size: int = 0, hotwords: Optional[str] = None) -> TranscriptionOptions:
         temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
         return TranscriptionOptions(
             beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
-            repetition_penalty=1, no_repeat_ngram_size=0,
+            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
             log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
             compression_ratio_threshold=compression_ratio_threshold, condition_on_previous_text=False,
             prompt_reset_on_temperature=0.5, temperatures=temps, initial_prompt=initial_prompt, prefix=None,
@@ -965,7 +973,7 @@ class BatchedInferencePipeline:
             without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
             append_punctuations=append_punctuations, multilingual=False, max_new_tokens=max_new_tokens,
-            clip_timestamps=clip_timestamps or "0", hallucination_silence_threshold=None, hotwords=None)
+            clip_timestamps=clip_timestamps or "0", hallucination_silence_threshold=None, hotwords=hotwords)
 
     @staticmethod
     def _info(prep: dict, options: TranscriptionOptions) -> TranscriptionInfo:
