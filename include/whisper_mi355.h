@@ -111,13 +111,21 @@ int wm_reserve(wm_engine* e, int32_t n_slots, int32_t n_hyp, void* stream);
 int wm_cross_kv(wm_engine* e, const void* d_enc, int32_t B, int32_t slot0, void* stream);
 
 /* ctranslate2 Whisper.generate(encoder_output, prompts, ...) [FW↑] as faster-whisper
- * generate_with_fallback calls it: all windows share one prompt length; greedy (beam_size 1,
- * temperature 0), beam search (beam_size > 1, patience, length_penalty) or sampling (temperature > 0,
- * num_hypotheses = best_of).  Logit rules, log-softmax and selection run on the device. */
+ * generate_with_fallback calls it: greedy (beam_size 1, temperature 0), beam search (beam_size > 1, patience,
+ * length_penalty) or sampling (temperature > 0, num_hypotheses = best_of).  Logit rules, log-softmax and selection
+ * run on the device.
+ * Shared by all windows of one call: the decode form and its parameters (beam_size, patience, length_penalty,
+ * temperature, num_hypotheses, seed), the logit rules (suppress list, suppress_blank, max_initial_timestamp_index,
+ * with_timestamps, repetition_penalty, no_repeat_ngram_size) and the scheduling fields (check_every, max_rows,
+ * compact).  Per window: the cross-KV slot, the prompt and, since ABI 4, its length (h_prompt_lens), the position
+ * its no-speech probability is read at (h_sot_indices) and its total length limit (h_max_lengths), so windows
+ * whose previous-text prompts differ in length (faster-whisper's condition_on_previous_text, one file per window)
+ * decode in the same passes.  Each window's result is what a call with that window alone computes, to the f32
+ * rounding of the pass's GEMM / attention routes (which follow the pass's row count). */
 typedef struct wm_generate_args {
   int32_t n_windows;
   const int32_t* h_slots;        /* [n_windows] cross-KV slot of each window */
-  int32_t prompt_len;
+  int32_t prompt_len;            /* prompt length of every window (ABI 4 h_prompt_lens: the row stride of h_prompts) */
   const int32_t* h_prompts;      /* [n_windows][prompt_len] */
   int32_t sot_index;             /* position of <|startoftranscript|> in the prompt; -1: no no_speech_prob */
   int32_t beam_size;
@@ -176,6 +184,27 @@ typedef struct wm_generate_args {
    * them (greedy, sampling, beam, the row-set decodes: a refilled row's history restarts with its new window). */
   float repetition_penalty;
   int32_t no_repeat_ngram_size;
+  /* ---- ABI 4 (wm_abi_version() >= 4) */
+  /* Ragged prompts: per-window prompt length, sot position and length limit, each [n_windows] or NULL.  A zero-filled
+   * tail (three NULLs) keeps the ABI 3 behaviour exactly, and launches the same kernels.
+   * h_prompt_lens: NULL: every window's prompt is prompt_len tokens.  Otherwise prompt_len is the row stride of
+   * h_prompts and window w's prompt is the first h_prompt_lens[w] tokens of its row; the padding behind it is neither
+   * validated nor read.
+   * h_sot_indices: NULL: sot_index holds for every window.  Otherwise window w's no-speech probability is read at its
+   * own position h_sot_indices[w] (< 0: none for that window, h_no_speech[w] = 0).
+   * h_max_lengths: NULL: max_length holds for every window.  Otherwise h_max_lengths[w] is the total decoder length
+   * of window w including its prompt (faster-whisper's max_new_tokens is len(prompt) + max_new_tokens per window).
+   * max_length stays the row stride of h_tokens and of the record arrays and must be >= every entry.
+   * The call fails (-1, before anything is launched, the message names the window) on a prompt length <= 0 or
+   * > prompt_len, a prompt length >= that window's max length, a max length > n_text_ctx or > max_length, a sot index
+   * >= that window's prompt length, or a token outside the vocabulary inside a prompt.  Every decode form takes
+   * ragged prompts (greedy, sampling with any num_hypotheses, beam search; max_rows 0, max_rows below the windows,
+   * compact); the rules of ABI 3 start at each window's own prompt length, and the sampling step index counts the
+   * window's own generated tokens.  The logit rules, the seed and the decode form stay shared.  h_steps / h_stats keep
+   * their meaning. */
+  const int32_t* h_prompt_lens;
+  const int32_t* h_sot_indices;
+  const int32_t* h_max_lengths;
 } wm_generate_args;
 /* Failure contract: a NaN / inf logits row or a row whose rules allow no token, detected on the device, fails the
  * call (-1, wm_last_error names the window and step) instead of emitting a token. */

@@ -13,6 +13,11 @@ temperature 0, so the default fallback ladder costs nothing extra); --random-wei
 average log-probability (about -7) fails the -1.0 threshold on every window, so the fallback re-decodes every
 window at five temperatures (best_of 5).  Prints one JSON line.
 usage: python tools/bench_worker_call.py [--minutes-seq 5] [--minutes-tp 60] [--model large-v3]
+
+--files 1,2,4,8,16,32: the sequential mode over several pending files instead (WhisperModel.transcribe_many, the
+worker's call per file): for each N, N distinct clips of --minutes-seq minutes with N files in flight; one JSON line per
+point with the RTFx summed over the files and the milliseconds per decoder pass of the shared first-pass decodes (wall
+time inside engine.generate over its pass count); N = 1 is `transcribe` on one file.
 """
 import argparse
 import json
@@ -46,6 +51,50 @@ def worker_call(model, wav, temperature=None):
     return time.perf_counter() - t, " ".join(parts), info, len(segs), len(vtt)
 
 
+def many_files(model, args, spec, tmp):
+    counts = [int(v) for v in args.files.split(",")]
+    n_win = int(round(args.minutes_seq * 2))
+    paths = []
+    for f in range(max(counts)):
+        path = os.path.join(tmp, f"file{f}.wav")
+        write_wav(path, np.concatenate([speech_like(30.0, 100 * f + i) for i in range(n_win)]))
+        paths.append(path)
+    audio_s = n_win * 30.0
+    eng = model.engine
+    acc = {"s": 0.0, "passes": 0, "rows": 0, "calls": 0}
+    inner = eng.generate
+
+    def timed_generate(*a, **kw):
+        st = {}
+        kw["stats"] = st
+        t = time.perf_counter()
+        r = inner(*a, **kw)
+        acc["s"] += time.perf_counter() - t
+        acc["passes"] += st["passes"]
+        acc["rows"] += st["row_steps"]
+        acc["calls"] += 1
+        return r
+
+    eng.generate = timed_generate
+    kw = dict(language=None, task="transcribe", beam_size=5, vad_filter=True)
+    if args.temperature is not None:
+        kw["temperature"] = args.temperature
+    list(model.transcribe(paths[0], **kw)[0])                      # warm-up
+    for n in counts:
+        acc.update(s=0.0, passes=0, rows=0, calls=0)
+        t = time.perf_counter()
+        if n == 1:
+            nseg = len(list(model.transcribe(paths[0], **kw)[0]))
+        else:
+            nseg = sum(len(s) for s, _ in model.transcribe_many(paths[:n], max_files=n, **kw))
+        dt = time.perf_counter() - t
+        print(json.dumps({"model": args.model, "weights": spec, "files_in_flight": n, "call": "transcribe" if n == 1 else
+                          "transcribe_many", "audio_s_per_file": audio_s, "wall_s": round(dt, 3),
+                          "rtfx_sum": round(n * audio_s / dt, 2), "segments": nseg, "generate_calls": acc["calls"],
+                          "decoder_passes": acc["passes"], "ms_per_decoder_pass": round(1e3 * acc["s"] / max(acc["passes"], 1), 4),
+                          "rows_per_pass": round(acc["rows"] / max(acc["passes"], 1), 2)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="large-v3")
@@ -58,12 +107,16 @@ def main():
                     help="plain random-init weights (every window fails the log-prob threshold and is re-decoded at "
                          "five temperatures); default: the margin-planted model, whose windows pass like a trained one")
     ap.add_argument("--no-graph", action="store_true", help="decode steps launched eagerly (decode_graph=0)")
+    ap.add_argument("--files", default=None,
+                    help="comma-separated numbers of files in flight: measure transcribe_many instead (module docstring)")
     args = ap.parse_args()
     spec = f"synthetic:{args.model}:0" + ("" if args.random_weights else ":margin")
     model = WhisperModel(spec, device="cpu", compute_type="int8", eot_after=110)
     if args.no_graph:
         model.engine.set_option("decode_graph", 0)
     tmp = tempfile.mkdtemp()
+    if args.files:
+        return many_files(model, args, spec, tmp)
 
     def clip(minutes, name):
         n = int(round(minutes * 2))

@@ -11,7 +11,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VLOG_AMD_LIB") or os.path.join(_HERE, "libwhisper_mi355.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 # Every entry point include/whisper_mi355.h declares (tests check the library exports all of them).
 SYMBOLS = (
@@ -44,6 +44,9 @@ class GenerateArgsC(C.Structure):
         ("h_token_logprobs_other", C.POINTER(C.c_float)), ("h_stats", C.POINTER(C.c_int64)),
         # ABI 3
         ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32),
+        # ABI 4: ragged prompts, each [n_windows] or NULL
+        ("h_prompt_lens", C.POINTER(C.c_int32)), ("h_sot_indices", C.POINTER(C.c_int32)),
+        ("h_max_lengths", C.POINTER(C.c_int32)),
     ]
 
 

@@ -183,6 +183,7 @@ struct wm_engine {
   // row-set decode (generate_rows): per-window prompts / slots, slot -> output id, output tables by window, and
   // the event upload (pass rows, row set, logit rows, starts)
   DevBuf d_win_prompt, d_win_slot, d_hyp_out, d_res_tok, d_res_len, d_res_cum, d_res_ns, d_res_lp, d_res_lp_o, d_ev;
+  DevBuf d_hyp_begin, d_hyp_maxlen, d_win_len, d_win_maxlen;   // ragged prompts (search.h hyp_begin / hyp_maxlen)
   std::vector<int> h_ev;     // host image of d_ev (kept alive until the next poll syncs the stream)
   int dbg_nan_row = -1;      // TEST ONLY (wm_set_option "debug_nan_row"): NaN logits row before every selection
   int dbg_nan_count = 1;     // TEST ONLY ("debug_nan_count"): rows [debug_nan_row, + count) (a whole beam group: nlive 0)
@@ -1011,8 +1012,80 @@ struct StepGraph {
   }
 };
 
-void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st);
-void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st);
+// The per-window view of a call's prompts (ABI 4).  `ragged` is set when the caller passed any of h_prompt_lens /
+// h_sot_indices / h_max_lengths: the decode loops then take every length from here and the selection kernels from the
+// device tables; without it they run exactly the one-length code (len[w] = prompt_len for all w is never consulted).
+struct WinArgs {
+  bool ragged = false;
+  bool same_len = true;           // every window has the same prompt length (then the prefill keeps its grouping)
+  int Pmax = 0;                   // the longest prompt (scratch sizing, pass limit)
+  int max_gen = 0;                // the most tokens any window may generate: max over w of ml[w] - len[w]
+  std::vector<int> len, sot, ml;  // [W]
+};
+
+// Validates the prompts of a call (nothing has been launched yet) and resolves the per-window values.
+WinArgs window_args(wm_engine* e, const wm_generate_args* a) {
+  const int C = e->dm.n_text_ctx, V = e->dm.n_vocab;
+  const int W = a->n_windows, P = a->prompt_len;
+  WinArgs wa;
+  wa.ragged = a->h_prompt_lens || a->h_sot_indices || a->h_max_lengths;
+  if (!wa.ragged) {
+    if (P <= 0 || P >= a->max_length || a->max_length > C) throw std::runtime_error("generate: bad prompt_len/max_length");
+    if (a->sot_index >= P) throw std::runtime_error("generate: sot_index outside the prompt");
+    for (int i = 0; i < W * P; ++i)
+      if (a->h_prompts[i] < 0 || a->h_prompts[i] >= V) throw std::runtime_error("generate: prompt token out of the vocabulary");
+    wa.Pmax = P;
+    wa.max_gen = a->max_length - P;
+    return wa;
+  }
+  if (P <= 0) throw std::runtime_error("generate: bad prompt_len/max_length");
+  wa.len.resize(W); wa.sot.resize(W); wa.ml.resize(W);
+  for (int w = 0; w < W; ++w) {
+    const std::string who = "generate: window " + std::to_string(w) + ": ";
+    const int n = a->h_prompt_lens ? a->h_prompt_lens[w] : P;
+    const int ml = a->h_max_lengths ? a->h_max_lengths[w] : a->max_length;
+    const int sot = a->h_sot_indices ? a->h_sot_indices[w] : a->sot_index;
+    if (n <= 0 || n > P)
+      throw std::runtime_error(who + "prompt length " + std::to_string(n) + " outside [1, prompt_len = " + std::to_string(P) + "]");
+    if (ml > C || ml > a->max_length)
+      throw std::runtime_error(who + "max length " + std::to_string(ml) + " above n_text_ctx or max_length");
+    if (n >= ml)
+      throw std::runtime_error(who + "prompt length " + std::to_string(n) + " leaves no room below its max length " +
+                               std::to_string(ml));
+    if (sot >= n) throw std::runtime_error(who + "sot index " + std::to_string(sot) + " outside its prompt");
+    for (int p = 0; p < n; ++p) {                 // the padding behind the prompt is neither validated nor read
+      const int t = a->h_prompts[(size_t)w * P + p];
+      if (t < 0 || t >= V)
+        throw std::runtime_error(who + "prompt token " + std::to_string(t) + " at position " + std::to_string(p) +
+                                 " out of the vocabulary");
+    }
+    wa.len[w] = n; wa.ml[w] = ml; wa.sot[w] = sot;
+    wa.Pmax = std::max(wa.Pmax, n);
+    wa.max_gen = std::max(wa.max_gen, ml - n);
+    if (n != wa.len[0]) wa.same_len = false;
+  }
+  return wa;
+}
+
+// Uploads the per-window tables of a ragged row-set decode and points the selection at the per-hypothesis ones
+// (n_hyp entries, filled by hyp_start / beam_start as slots take windows).
+void upload_window_tables(wm_engine* e, const WinArgs& wa, int n_hyp, SearchParams* sp, BeamParams* bp, hipStream_t st) {
+  const size_t W = wa.len.size();
+  e->d_win_len.ensure(W * 4);
+  e->d_win_maxlen.ensure(W * 4);
+  e->d_hyp_begin.ensure((size_t)n_hyp * 4);
+  e->d_hyp_maxlen.ensure((size_t)n_hyp * 4);
+  HIP_OK(hipMemcpyAsync(e->d_win_len.p, wa.len.data(), W * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(e->d_win_maxlen.p, wa.ml.data(), W * 4, hipMemcpyHostToDevice, st));
+  // slots that no window has taken yet are skipped by the selection (done), but keep their rows defined
+  HIP_OK(hipMemsetAsync(e->d_hyp_begin.p, 0, (size_t)n_hyp * 4, st));
+  HIP_OK(hipMemsetAsync(e->d_hyp_maxlen.p, 0, (size_t)n_hyp * 4, st));
+  sp->hyp_begin = e->d_hyp_begin.as<int>(); sp->hyp_maxlen = e->d_hyp_maxlen.as<int>();
+  if (bp) { bp->hyp_begin = sp->hyp_begin; bp->hyp_maxlen = sp->hyp_maxlen; }
+}
+
+void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, hipStream_t st);
+void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, hipStream_t st);
 
 void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   check_weights(e);
@@ -1020,8 +1093,10 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   const int C = m.n_text_ctx, V = m.n_vocab;
   const int W = a->n_windows, P = a->prompt_len;
   if (W <= 0) return;
-  if (P <= 0 || P >= a->max_length || a->max_length > C) throw std::runtime_error("generate: bad prompt_len/max_length");
-  if (a->sot_index >= P) throw std::runtime_error("generate: sot_index outside the prompt");
+  const WinArgs wa = window_args(e, a);
+  const bool rag = wa.ragged;
+  auto plen = [&](int w) { return rag ? wa.len[w] : P; };
+  auto psot = [&](int w) { return rag ? wa.sot[w] : a->sot_index; };
   if (!(a->repetition_penalty >= 0.f) || std::isinf(a->repetition_penalty))
     throw std::runtime_error("generate: repetition_penalty must be a finite value > 0 (0 or 1: off)");
   if (a->no_repeat_ngram_size < 0 || a->no_repeat_ngram_size > a->max_length)
@@ -1033,16 +1108,14 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   if (beam && a->beam_size > 8) throw std::runtime_error("generate: beam_size <= 8 supported");
   for (int w = 0; w < W; ++w)
     if (a->h_slots[w] < 0 || a->h_slots[w] >= e->n_slots) throw std::runtime_error("generate: slot out of range");
-  for (int i = 0; i < W * P; ++i)
-    if (a->h_prompts[i] < 0 || a->h_prompts[i] >= V) throw std::runtime_error("generate: prompt token out of the vocabulary");
   if (a->max_rows < 0) throw std::runtime_error("generate: max_rows must be >= 0");
   if (per == 1 && !beam && ((a->max_rows > 0 && a->max_rows < W) || a->compact)) {
-    generate_rows(e, a, st);
+    generate_rows(e, a, wa, st);
     return;
   }
   if (beam && a->max_rows > 0 && a->max_rows < NH) {
     if (a->max_rows < per) throw std::runtime_error("generate: max_rows must hold one window's beam");
-    generate_rows_beam(e, a, st);
+    generate_rows_beam(e, a, wa, st);
     return;
   }
   if (a->max_rows > 0 && a->max_rows < W) throw std::runtime_error("generate: max_rows needs greedy, beam search or num_hypotheses 1");
@@ -1053,6 +1126,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
 
   // ---- host-side init of the state tables
   std::vector<int> tokens((size_t)NH * C, 0), lin((size_t)NH * C, 0), seq_len(NH, P), zeros(NH, 0), hyp_slot(NH);
+  std::vector<int> hyp_ml;                         // ragged: the per-hypothesis length limits (seq_len holds the prompt lengths)
   std::vector<float> cum(NH, 0.f);
   // Beam search: the hypotheses of a window share its prompt, so the prompt is prefilled once per window (into
   // the first hypothesis' self-KV rows) and every hypothesis' lineage points its prompt positions there (the
@@ -1061,9 +1135,20 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   for (int h = 0; h < NH; ++h) {
     const int w = h / per;
     hyp_slot[h] = a->h_slots[w];
-    for (int p = 0; p < P; ++p) tokens[(size_t)h * C + p] = a->h_prompts[(size_t)w * P + p];
-    for (int p = 0; p < C; ++p) lin[(size_t)h * C + p] = (beam && p < P) ? w * per : h;
+    const int Pw = plen(w);
+    seq_len[h] = Pw;
+    for (int p = 0; p < Pw; ++p) tokens[(size_t)h * C + p] = a->h_prompts[(size_t)w * P + p];
+    for (int p = 0; p < C; ++p) lin[(size_t)h * C + p] = (beam && p < Pw) ? w * per : h;
     if (beam && (h % per) != 0) cum[h] = -INFINITY;
+  }
+  if (rag) {
+    // the selection's per-hypothesis tables: a lockstep decode fills them once, here
+    hyp_ml.resize(NH);
+    for (int h = 0; h < NH; ++h) hyp_ml[h] = wa.ml[h / per];
+    e->d_hyp_begin.ensure((size_t)NH * 4);
+    e->d_hyp_maxlen.ensure((size_t)NH * 4);
+    HIP_OK(hipMemcpyAsync(e->d_hyp_begin.p, seq_len.data(), NH * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(e->d_hyp_maxlen.p, hyp_ml.data(), NH * 4, hipMemcpyHostToDevice, st));
   }
   HIP_OK(hipMemcpyAsync(e->d_tokens.p, tokens.data(), tokens.size() * 4, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(e->d_lin.p, lin.data(), lin.size() * 4, hipMemcpyHostToDevice, st));
@@ -1084,27 +1169,56 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   // ---- prefill: rows (h, p) for every prompt position of every prefilled hypothesis (beam: one per window)
   const int pf_per = beam ? per : 1;                 // hypotheses per prefilled row set
   const int n_pf = NH / pf_per;
-  const int rows = n_pf * P;
-  const int nlog = a->sot_index >= 0 ? 2 * NH : NH;
+  // Ragged prompts: the prefilled sets are ordered by CLASS, and each class is one decoder pass over its own rows.
+  // A class is a set of windows whose prompt rows form groups of one size g = (per / pf_per) * length, which is what
+  // the cross-attention form follows (launch_cross_attn: 2..32 rows of one window take the matrix-core kernel in the
+  // projected form, whose numerics differ from the f32 kernel's at bf16 rounding).  Windows whose g is at most 32
+  // keep exactly the grouping, and so the kernel, of a call of their own; all longer prompts share one pass with
+  // ungrouped rows (cross_group 1: the f32 kernels either way).  One length: one class, the pass as it always was.
+  const int gmul = per / pf_per;
+  std::vector<int> pf_cls(n_pf, 0), pf_order(n_pf);
+  for (int i = 0; i < n_pf; ++i) {
+    pf_order[i] = i;
+    const int g = gmul * plen(i * pf_per / per);
+    pf_cls[i] = (!rag || wa.same_len) ? g : (g <= 32 ? g : 0);
+  }
+  std::stable_sort(pf_order.begin(), pf_order.end(), [&](int x, int y) { return pf_cls[x] < pf_cls[y]; });
+  std::vector<int> pf_off(n_pf + 1, 0), pf_at(n_pf);       // set i's rows start at pf_at[i]
+  for (int k = 0; k < n_pf; ++k) {
+    const int i = pf_order[k];
+    pf_at[i] = pf_off[k];
+    pf_off[k + 1] = pf_off[k] + plen(i * pf_per / per);
+  }
+  const int rows = pf_off[n_pf];
+  bool any_sot = a->sot_index >= 0;
+  if (rag) {
+    any_sot = false;
+    for (int w = 0; w < W; ++w) any_sot |= wa.sot[w] >= 0;
+  }
+  const int nlog = any_sot ? 2 * NH : NH;
+  const bool one_class = pf_cls[pf_order[0]] == pf_cls[pf_order[n_pf - 1]];
   // the pass's final LayerNorm gathers its nlog logit rows into s_hb rows [0, nlog): with the beam's shared
   // prefill (rows = W * P) that can exceed the pass rows, so the row buffers hold max(rows, NH, nlog)
-  ensure_step(e, std::max(std::max(rows, NH), nlog), std::max(nlog, NH));
+  // (several classes: each pass writes its logit rows behind the nlog rows the selection reads, then they are moved)
+  ensure_step(e, std::max(std::max(rows, NH), nlog), (one_class ? 1 : 2) * std::max(nlog, NH));
+  std::vector<int> lr(nlog);
   {
-    std::vector<int> rt(rows), rp(rows), rh(rows), lr(nlog);
+    std::vector<int> rt(rows), rp(rows), rh(rows);
     for (int i = 0; i < n_pf; ++i)
-      for (int p = 0; p < P; ++p) {
-        const int r = i * P + p, h = i * pf_per;
+      for (int p = 0; p < plen(i * pf_per / per); ++p) {
+        const int r = pf_at[i] + p, h = i * pf_per;
         rt[r] = tokens[(size_t)h * C + p]; rp[r] = p; rh[r] = h;
       }
     for (int h = 0; h < NH; ++h) {            // a hypothesis' logits come from its row set's last prompt row
       const int i = h / pf_per;
-      lr[h] = i * P + P - 1;
-      if (a->sot_index >= 0) lr[NH + h] = i * P + a->sot_index;
+      lr[h] = pf_at[i] + plen(h / per) - 1;
+      // (a ragged call's window without a sot index reads a row of its own; its no-speech result is dropped below)
+      if (any_sot) lr[NH + h] = pf_at[i] + std::max(0, psot(h / per));
     }
     HIP_OK(hipMemcpyAsync(e->d_prow_tok.p, rt.data(), rows * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(e->d_prow_pos.p, rp.data(), rows * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(e->d_prow_hyp.p, rh.data(), rows * 4, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(e->d_logit_rows.p, lr.data(), nlog * 4, hipMemcpyHostToDevice, st));
+    if (one_class) HIP_OK(hipMemcpyAsync(e->d_logit_rows.p, lr.data(), nlog * 4, hipMemcpyHostToDevice, st));
     std::vector<int> ident(NH);
     for (int h = 0; h < NH; ++h) ident[h] = h;
     HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, ident.data(), NH * 4, hipMemcpyHostToDevice, st));
@@ -1112,12 +1226,47 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   }
   float* logits = e->s_logits.as<float>();
   int* err = e->d_n_active.as<int>() + 1;
-  decoder_pass(e, rows, e->d_prow_tok.as<int>(), e->d_prow_pos.as<int>(), e->d_prow_hyp.as<int>(), nullptr,
-               e->d_lin.as<int>(), e->d_logit_rows.as<int>(), nlog, logits, nullptr, 0, nullptr, (per / pf_per) * P, st, err);
-  if (a->sot_index >= 0) launch_no_speech(logits + (size_t)NH * V, V, V, NH, m.no_speech, e->d_ns.as<float>(), st);
+  if (one_class) {
+    decoder_pass(e, rows, e->d_prow_tok.as<int>(), e->d_prow_pos.as<int>(), e->d_prow_hyp.as<int>(), nullptr,
+                 e->d_lin.as<int>(), e->d_logit_rows.as<int>(), nlog, logits, nullptr, 0, nullptr,
+                 std::max(1, pf_cls[0]), st, err);
+  } else {
+    // every class' logit rows (relative to its first pass row) and the rows the selection expects them at, uploaded
+    // once: [src rows of all classes | destination rows of all classes], nlog entries each
+    float* tmp = logits + (size_t)nlog * V;
+    struct Cls { int r0, nr, at, nc, group; };
+    std::vector<Cls> classes;
+    std::vector<int> tab(2 * (size_t)nlog);
+    int at = 0;
+    for (int k0 = 0; k0 < n_pf;) {
+      const int cls = pf_cls[pf_order[k0]];
+      int k1 = k0;
+      while (k1 < n_pf && pf_cls[pf_order[k1]] == cls) ++k1;
+      const int r0 = pf_off[k0], first = at;
+      for (int k = k0; k < k1; ++k)
+        for (int b = 0; b < pf_per; ++b) {
+          const int h = pf_order[k] * pf_per + b;
+          tab[at] = lr[h] - r0; tab[nlog + at] = h; ++at;
+          if (any_sot) { tab[at] = lr[NH + h] - r0; tab[nlog + at] = NH + h; ++at; }
+        }
+      classes.push_back({r0, pf_off[k1] - r0, first, at - first, cls > 0 ? cls : 1});
+      k0 = k1;
+    }
+    e->d_logit_rows.ensure(tab.size() * 4);
+    HIP_OK(hipMemcpyAsync(e->d_logit_rows.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st));         // (tab goes out of scope; the only host wait of the prefill)
+    const int* dtab = e->d_logit_rows.as<int>();
+    for (const Cls& c : classes) {
+      decoder_pass(e, c.nr, e->d_prow_tok.as<int>() + c.r0, e->d_prow_pos.as<int>() + c.r0, e->d_prow_hyp.as<int>() + c.r0,
+                   nullptr, e->d_lin.as<int>(), dtab + c.at, c.nc, tmp, nullptr, 0, nullptr, c.group, st, err);
+      launch_rows_scatter(tmp, logits, dtab + nlog + c.at, c.nc, V, st);     // one launch moves the class' logit rows
+    }
+  }
+  if (any_sot) launch_no_speech(logits + (size_t)NH * V, V, V, NH, m.no_speech, e->d_ns.as<float>(), st);
 
   SearchParams sp = search_params(e, a, logits, P);
   sp.mode = beam ? 1 : (sampling ? 2 : 0); sp.topk = beam ? a->beam_size + 1 : 1;
+  if (rag) { sp.hyp_begin = e->d_hyp_begin.as<int>(); sp.hyp_maxlen = e->d_hyp_maxlen.as<int>(); }
   if (rec) {
     sp.tok_lp = e->d_tok_lp.as<float>();
     if (!beam) sp.tok_lp_other = e->d_tok_lp_o.as<float>();
@@ -1129,6 +1278,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   bp.seq_len = sp.seq_len; bp.cum = sp.cum; bp.done = sp.done; bp.row_tok = sp.row_tok; bp.row_pos = sp.row_pos;
   bp.fin_tok = e->d_fin_tok.as<int>(); bp.fin_len = e->d_fin_len.as<int>(); bp.fin_cum = e->d_fin_cum.as<float>();
   bp.n_fin = e->d_n_fin.as<int>(); bp.n_active = sp.n_active;
+  bp.hyp_begin = sp.hyp_begin; bp.hyp_maxlen = sp.hyp_maxlen;
   if (rec && beam) {
     bp.tok_lp = e->d_tok_lp.as<float>();
     bp.fin_lp = e->d_fin_lp.as<float>();
@@ -1145,7 +1295,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   int steps = 1;
   long long row_steps = NH;                      // the prefill pass selects every hypothesis' first token
   int captures = 0;
-  const int max_steps = a->max_length - P;      // generated tokens (incl. the final one) <= max_length - P
+  const int max_steps = wa.max_gen;             // generated tokens (incl. the final one) <= max_length - P, per window
   const int check = std::max(1, a->check_every);
   // A decode step's launches are identical from step to step: every per-step quantity (tokens, positions,
   // lineage, done flags, sequence lengths) lives in device memory and is advanced by the select kernels, so
@@ -1260,7 +1410,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   HIP_OK(hipMemcpyAsync(out_len.data(), e->d_seq_len.p, NH * 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipMemcpyAsync(out_cum.data(), e->d_cum.p, NH * 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipMemcpyAsync(poll, e->d_n_active.p, sizeof(poll), hipMemcpyDeviceToHost, st));
-  if (a->sot_index >= 0) HIP_OK(hipMemcpyAsync(ns.data(), e->d_ns.p, NH * 4, hipMemcpyDeviceToHost, st));
+  if (any_sot) HIP_OK(hipMemcpyAsync(ns.data(), e->d_ns.p, NH * 4, hipMemcpyDeviceToHost, st));
   if (rec) {
     out_lp.resize((size_t)NH * C);
     HIP_OK(hipMemcpyAsync(out_lp.data(), e->d_tok_lp.p, out_lp.size() * 4, hipMemcpyDeviceToHost, st));
@@ -1289,6 +1439,8 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   auto norm = [&](float c, int n) { return c / std::pow((float)std::max(n, 1), lp); };
   const int ML = a->max_length;
   for (int w = 0; w < W; ++w) {
+    const int P = plen(w);                      // this window's own prompt length and length limit from here on
+    const int MLw = rag ? wa.ml[w] : ML;
     int best_len = 0;
     float best_cum = 0.f, best_score = -INFINITY;
     const int* best_ptr = nullptr;
@@ -1330,10 +1482,10 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
     a->h_lengths[w] = best_len;
     a->h_scores[w] = best_score;
     if (a->h_cum_logprob) a->h_cum_logprob[w] = best_cum;
-    if (a->h_no_speech) a->h_no_speech[w] = ns[w * per];
+    if (a->h_no_speech) a->h_no_speech[w] = psot(w) >= 0 ? ns[w * per] : 0.f;
     if (rec) {
       // one record per generated token, plus the final <|endoftext|> when the window ended on it
-      const int nr = std::min(ML, best_len + (P + best_len < ML ? 1 : 0));
+      const int nr = std::min(ML, best_len + (P + best_len < MLw ? 1 : 0));
       for (int i = 0; i < nr; ++i) {
         a->h_token_logprobs[(size_t)w * ML + i] = best_lp ? best_lp[i] : NAN;
         if (a->h_token_logprobs_other) a->h_token_logprobs_other[(size_t)w * ML + i] = best_lpo ? best_lpo[i] : NAN;
@@ -1361,13 +1513,22 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
 // graph stays valid; once the queue is empty and compaction is on, the live rows are packed densely when they
 // fall to 7/8 of the pass (row_compact_8ths; re-capture for the new count).  A finished hypothesis' tokens are copied to the
 // per-window output tables by the block that ends it (search.hip), since its slot is then reused.
-void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
+void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, hipStream_t st) {
   const auto& m = e->dm;
   const int C = m.n_text_ctx, V = m.n_vocab;
   const int W = a->n_windows, P = a->prompt_len;
   const int R = a->max_rows > 0 ? std::min(a->max_rows, W) : W;
   const bool rec = a->h_token_logprobs != nullptr;
   const int ML = a->max_length;
+  // ragged prompts: P stays the row stride of h_prompts; a window's own values come from wa
+  const bool rag = wa.ragged;
+  auto plen = [&](int w) { return rag ? wa.len[w] : P; };
+  auto psot = [&](int w) { return rag ? wa.sot[w] : a->sot_index; };
+  bool any_sot = a->sot_index >= 0;
+  if (rag) {
+    any_sot = false;
+    for (int w = 0; w < W; ++w) any_sot |= wa.sot[w] >= 0;
+  }
   reserve(e, e->n_slots, R);
   // per-window inputs and outputs
   e->d_win_prompt.ensure((size_t)W * P * 4);
@@ -1393,7 +1554,7 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
     upload_suppress(e, a, st);                 // (synchronises: `ones` goes out of scope)
   }
   // pass rows: R decode rows + P prompt rows per starting window; logits rows: R + one sot row per start
-  ensure_step(e, R * (1 + P), 2 * R);
+  ensure_step(e, R * (1 + wa.Pmax), 2 * R);
   float* logits = e->s_logits.as<float>();
   int* counters = e->d_n_active.as<int>();     // [0] live hypotheses, [1..3] error word
   int* err = counters + 1;
@@ -1403,6 +1564,7 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   sp.row_hyp = e->d_row_hyp.as<int>();
   sp.hyp_out = e->d_hyp_out.as<int>();
   sp.res_tok = e->d_res_tok.as<int>(); sp.res_len = e->d_res_len.as<int>(); sp.res_cum = e->d_res_cum.as<float>();
+  if (rag) upload_window_tables(e, wa, R, &sp, nullptr, st);
   if (rec) {
     sp.tok_lp = e->d_tok_lp.as<float>(); sp.tok_lp_other = e->d_tok_lp_o.as<float>();
     sp.res_lp = e->d_res_lp.as<float>(); sp.res_lp_other = e->d_res_lp_o.as<float>();
@@ -1422,10 +1584,10 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   std::vector<std::pair<int, int>> starts;      // (slot, window)
   auto event = [&](hipStream_t s) {
     const int nr = (int)new_row_hyp.size(), nst = (int)starts.size();
-    const int nsot = a->sot_index >= 0 ? nst : 0;
-    int np = 0, n_live = 0;
+    const int nsot = any_sot ? nst : 0;
+    int np = 0, n_live = 0, ks = 0;
     for (int c : carry) {
-      np += c >= 0 ? 1 : (c == -1 ? P : 0);
+      np += c >= 0 ? 1 : (c == -1 ? plen(starts[ks++].second) : 0);
       n_live += c >= -1;
     }
     // upload: ptok, ppos, phyp, psrc [np] | row set [nr] | logits rows [nr + nsot] | start slots, windows [nst] | live
@@ -1442,9 +1604,11 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
         lr[r] = i++;
       } else if (carry[r] == -1) {
         const int h = starts[k].first, w = starts[k].second;
-        for (int p = 0; p < P; ++p, ++i) {
+        const int Pw = plen(w), sot = psot(w);
+        // (a window without a sot index in a call that has some: its row defaults to 0 and its result is dropped)
+        for (int p = 0; p < Pw; ++p, ++i) {
           ptok[i] = a->h_prompts[(size_t)w * P + p]; ppos[i] = p; phyp[i] = h; psrc[i] = -1;
-          if (p == a->sot_index) lr[nr + k] = i;
+          if (p == sot) lr[nr + k] = i;
         }
         lr[r] = i - 1;                          // the last prompt position predicts the first token
         hs[k] = h; ws[k] = w;
@@ -1462,7 +1626,9 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
     launch_rows_fill(np, dpsrc, dptok, dppos, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
     launch_hyp_start(nst, dhs, dws, e->d_win_prompt.as<int>(), P, e->d_win_slot.as<int>(), C, e->d_tokens.as<int>(),
                      e->d_seq_len.as<int>(), e->d_done.as<int>(), e->d_cum.as<float>(), e->d_hyp_slot.as<int>(),
-                     e->d_hyp_out.as<int>(), s);
+                     e->d_hyp_out.as<int>(), s, rag ? e->d_win_len.as<int>() : nullptr,
+                     rag ? e->d_win_maxlen.as<int>() : nullptr, rag ? e->d_hyp_begin.as<int>() : nullptr,
+                     rag ? e->d_hyp_maxlen.as<int>() : nullptr);
     HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, drh, (size_t)nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_OK(hipMemcpyAsync(counters, dws + nst, 4, hipMemcpyDeviceToDevice, s));
     decoder_pass(e, np, dptok, dppos, dphyp, e->d_done.as<int>(), nullptr, dlr, nr + nsot, logits, nullptr, 0, nullptr, 1, s,
@@ -1508,7 +1674,7 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   std::vector<int> h_done(R);
   int h_cnt[4] = {0, 0, 0, 0};
   // every window's tokens need at most max_length - P steps; a generous bound against a stuck loop
-  const long long pass_limit = (long long)(W / std::max(1, R) + 2) * (ML - P + check + 2) + 16;
+  const long long pass_limit = (long long)(W / std::max(1, R) + 2) * (wa.max_gen + check + 2) + 16;
   try {
     // first pass: the first R windows start
     carry.assign(R, -1);
@@ -1615,9 +1781,9 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
     a->h_lengths[w] = n;
     a->h_scores[w] = res_cum[w] / std::pow((float)std::max(n, 1), lp);
     if (a->h_cum_logprob) a->h_cum_logprob[w] = res_cum[w];
-    if (a->h_no_speech) a->h_no_speech[w] = res_ns[w];
+    if (a->h_no_speech) a->h_no_speech[w] = psot(w) >= 0 ? res_ns[w] : 0.f;
     if (rec) {
-      const int nr = std::min(ML, n + (P + n < ML ? 1 : 0));
+      const int nr = std::min(ML, n + (plen(w) + n < (rag ? wa.ml[w] : ML) ? 1 : 0));
       for (int i = 0; i < nr; ++i) {
         a->h_token_logprobs[(size_t)w * ML + i] = res_lp[(size_t)w * C + i];
         if (a->h_token_logprobs_other) a->h_token_logprobs_other[(size_t)w * ML + i] = res_lpo[(size_t)w * C + i];
@@ -1713,7 +1879,7 @@ void dtw_run(wm_engine* e, const float* d_x, int N, int M, int* h_i, int* h_j, i
 // The K rows of a group stay together (its window's cross panels are read once for them), the row set keeps its
 // groups in place while windows wait (the step graph stays valid), and once nothing waits the finished groups'
 // rows are dropped at 7/8 (beam passes are GEMM-row-bound).  No per-step records in this form.
-void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
+void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, hipStream_t st) {
   const auto& m = e->dm;
   const int C = m.n_text_ctx, V = m.n_vocab;
   const int W = a->n_windows, P = a->prompt_len, K = a->beam_size;
@@ -1723,6 +1889,15 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
   const int max_cand = std::max(1, (int)std::lround(a->beam_size * a->patience));
   if (max_cand > 16) throw std::runtime_error("generate: beam_size * patience must be <= 16");
   if (a->h_token_logprobs) throw std::runtime_error("generate: per-step records need max_rows 0 with beam search");
+  // ragged prompts: P stays the row stride of h_prompts; a window's own values come from wa
+  const bool rag = wa.ragged;
+  auto plen = [&](int w) { return rag ? wa.len[w] : P; };
+  auto psot = [&](int w) { return rag ? wa.sot[w] : a->sot_index; };
+  bool any_sot = a->sot_index >= 0;
+  if (rag) {
+    any_sot = false;
+    for (int w = 0; w < W; ++w) any_sot |= wa.sot[w] >= 0;
+  }
   reserve(e, e->n_slots, NH);
   e->d_win_prompt.ensure((size_t)W * P * 4);
   e->d_win_slot.ensure((size_t)W * 4);
@@ -1738,7 +1913,7 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
   }
   // pass rows: every hypothesis row + P prompt rows per starting group; logits rows: one per hypothesis row + one
   // sot row per start
-  ensure_step(e, NH + G * std::max(P, K), NH + G);
+  ensure_step(e, NH + G * std::max(wa.Pmax, K), NH + G);
   float* logits = e->s_logits.as<float>();
   int* counters = e->d_n_active.as<int>();
   int* err = counters + 1;
@@ -1752,6 +1927,7 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
   bp.seq_len = sp.seq_len; bp.cum = sp.cum; bp.done = sp.done; bp.row_tok = sp.row_tok; bp.row_pos = sp.row_pos;
   bp.fin_tok = e->d_fin_tok.as<int>(); bp.fin_len = e->d_fin_len.as<int>(); bp.fin_cum = e->d_fin_cum.as<float>();
   bp.n_fin = e->d_n_fin.as<int>(); bp.n_active = sp.n_active;
+  if (rag) upload_window_tables(e, wa, NH, &sp, &bp, st);
 
   // host view: the row set is a list of groups (K rows each, in order); group g decodes window gwin[g] while glive[g]
   std::vector<int> set(G), gwin(G, -1);
@@ -1779,6 +1955,7 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
     HIP_OK(hipStreamSynchronize(s));
     for (int g : gs) {
       const int w = gwin[g];
+      const int P = plen(w);                    // the window's own prompt length
       struct C2 { const int* t; int n; float c; };
       std::vector<C2> cands;
       for (int i = 0; i < std::min(f_n[g], max_cand); ++i) {
@@ -1822,16 +1999,17 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
   // A starting group's P prompt rows are padded to K with copies of its last prompt row (same hypothesis, position
   // and token: identical self-KV writes), so every group of the pass holds K rows of one window and the
   // cross-attention keeps its per-window grouping (prompts longer than K rows: ungrouped rows).
-  const int PR = std::max(P, K);
-  const int ev_group = P <= K ? K : 1;
+  // (Prompts of different lengths: ungrouped rows too.)
+  const int PR = std::max(wa.Pmax, K);
+  const int ev_group = (!rag || wa.same_len) && wa.Pmax <= K ? K : 1;
   auto event = [&](hipStream_t s) {
     const int ng = (int)nset.size(), nr = ng * K, nst = (int)starts.size();
-    const int nsot = a->sot_index >= 0 ? nst : 0;
+    const int nsot = any_sot ? nst : 0;
     std::vector<int> start_of(G, -1);
     for (int k = 0; k < nst; ++k) start_of[starts[k].first] = k;
     int np = 0, n_live = 0;
     for (int g : nset) {
-      np += start_of[g] >= 0 ? (ev_group > 1 ? PR : P) : K;
+      np += start_of[g] >= 0 ? (ev_group > 1 ? PR : plen(starts[start_of[g]].second)) : K;
       n_live += (start_of[g] >= 0 || glive[g]) ? K : 0;
     }
     std::vector<int>& u = e->h_ev;
@@ -1845,13 +2023,14 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
       if (k >= 0) {
         const int w = starts[k].second;
         int last = 0;
-        for (int p = 0; p < P; ++p, ++i) {
+        const int Pw = plen(w), sot = psot(w);
+        for (int p = 0; p < Pw; ++p, ++i) {
           ptok[i] = a->h_prompts[(size_t)w * P + p]; ppos[i] = p; phyp[i] = h0; psrc[i] = -1;
-          if (p == a->sot_index) lr[nr + k] = i;
+          if (p == sot) lr[nr + k] = i;
           last = i;
         }
-        for (int p = P; ev_group > 1 && p < PR; ++p, ++i) {
-          ptok[i] = a->h_prompts[(size_t)w * P + P - 1]; ppos[i] = P - 1; phyp[i] = h0; psrc[i] = -1;
+        for (int p = Pw; ev_group > 1 && p < PR; ++p, ++i) {   // (grouped rows: every window has Pw = Pmax <= K)
+          ptok[i] = a->h_prompts[(size_t)w * P + Pw - 1]; ppos[i] = Pw - 1; phyp[i] = h0; psrc[i] = -1;
         }
         for (int b = 0; b < K; ++b, ++r) { rh[r] = h0 + b; lr[r] = last; }
         gsd[k] = g; wsd[k] = w;
@@ -1871,7 +2050,9 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
     launch_rows_fill(np, dpsrc, dptok, dppos, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
     launch_beam_start(nst, dgs, dws, K, e->d_win_prompt.as<int>(), P, e->d_win_slot.as<int>(), C, e->d_tokens.as<int>(),
                       e->d_lin.as<int>(), e->d_seq_len.as<int>(), e->d_done.as<int>(), e->d_cum.as<float>(),
-                      e->d_hyp_slot.as<int>(), e->d_n_fin.as<int>(), s);
+                      e->d_hyp_slot.as<int>(), e->d_n_fin.as<int>(), s, rag ? e->d_win_len.as<int>() : nullptr,
+                      rag ? e->d_win_maxlen.as<int>() : nullptr, rag ? e->d_hyp_begin.as<int>() : nullptr,
+                      rag ? e->d_hyp_maxlen.as<int>() : nullptr);
     HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, drh, (size_t)nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_OK(hipMemcpyAsync(counters, dws + nst, 4, hipMemcpyDeviceToDevice, s));
     decoder_pass(e, np, dptok, dppos, dphyp, e->d_done.as<int>(), e->d_lin.as<int>(), dlr, nr + nsot, logits, nullptr, 0,
@@ -1919,7 +2100,7 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
   const int refill_min = std::max(1, G / 16);
   std::vector<int> h_done(NH);
   int h_cnt[4] = {0, 0, 0, 0};
-  const long long pass_limit = (long long)(W / G + 2) * (ML - P + check + 2) + 16;
+  const long long pass_limit = (long long)(W / G + 2) * (wa.max_gen + check + 2) + 16;
   try {
     nset = set;
     starts.clear();
@@ -1995,7 +2176,7 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, hipStream_t st)
   if (nfinal != W) throw std::runtime_error("generate: beam row-set finished " + std::to_string(nfinal) + " of " +
                                             std::to_string(W) + " windows");
   for (int w = 0; w < W; ++w)
-    if (a->h_no_speech) a->h_no_speech[w] = res_ns[w];
+    if (a->h_no_speech) a->h_no_speech[w] = psot(w) >= 0 ? res_ns[w] : 0.f;
   if (a->h_steps) a->h_steps[0] = (int)passes;
   if (a->h_stats) {
     a->h_stats[0] = passes;
@@ -2324,7 +2505,7 @@ int* dec_proj_option(wm_engine* e, const std::string& k, const char* who, bool* 
 extern "C" {
 
 const char* wm_last_error(void) { return g_err.c_str(); }
-int32_t wm_abi_version(void) { return 3; }
+int32_t wm_abi_version(void) { return 4; }
 
 int wm_create(const wm_model_dims* dims, int32_t device, wm_engine** out) {
   try {
@@ -2393,7 +2574,7 @@ void wm_destroy(wm_engine* e) {
                     &e->a_next, &e->a_probs, &e->a_rowsum, &e->a_z, &e->a_mat, &e->a_cost, &e->a_trace, &e->a_pi,
                     &e->a_pj, &e->a_plen, &e->a_meta, &e->a_enc, &e->a_kv, &e->d_tok_lp, &e->d_tok_lp_o, &e->d_fin_lp, &e->d_win_prompt,
                     &e->d_win_slot, &e->d_hyp_out, &e->d_res_tok, &e->d_res_len, &e->d_res_cum, &e->d_res_ns, &e->d_res_lp,
-                    &e->d_res_lp_o, &e->d_ev})
+                    &e->d_res_lp_o, &e->d_ev, &e->d_hyp_begin, &e->d_hyp_maxlen, &e->d_win_len, &e->d_win_maxlen})
     b->release();
   if (e->st2) (void)hipStreamDestroy(e->st2);
   if (e->gst) (void)hipStreamDestroy(e->gst);

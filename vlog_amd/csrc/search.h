@@ -51,6 +51,10 @@ struct SearchParams {
   // launch_logits_select then runs the instantiations without them
   float rep_penalty;               // > 0
   int no_repeat_ngram;             // >= 0
+  // ragged prompts (both or neither; nullptr: sample_begin / max_length hold for every hypothesis): the prompt
+  // length and the total length limit of the window in each hypothesis slot, [n_hyp], device memory
+  const int* hyp_begin;
+  const int* hyp_maxlen;
 };
 
 struct BeamParams {
@@ -66,17 +70,28 @@ struct BeamParams {
   // tokens, then its <|endoftext|>)
   float* tok_lp;
   float* fin_lp;
+  // ragged prompts, as SearchParams (a window's values are read at its first hypothesis)
+  const int* hyp_begin;
+  const int* hyp_maxlen;
 };
 
 // Row-set decode bookkeeping (engine.cpp generate_rows).  Start hypotheses: slot hs[i] takes window ws[i] (prompt
-// win_prompt[ws[i]][0..P) into tokens, seq_len P, live, cum 0, its cross slot and output id).
+// win_prompt[ws[i]][0..P) into tokens, seq_len P, live, cum 0, its cross slot and output id).  Ragged prompts
+// (win_len != nullptr): P is the row stride of win_prompt, window w's prompt is its first win_len[w] tokens, and the
+// slot's rows of the selection tables become hyp_begin[h] = win_len[w], hyp_maxlen[h] = win_maxlen[w].
 void launch_hyp_start(int n, const int* hs, const int* ws, const int* win_prompt, int P, const int* win_slot, int n_ctx,
-                      int* tokens, int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out, hipStream_t st);
+                      int* tokens, int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out, hipStream_t st,
+                      const int* win_len = nullptr, const int* win_maxlen = nullptr, int* hyp_begin = nullptr,
+                      int* hyp_maxlen = nullptr);
 // Pass rows whose token / position live on the device: row i with src[i] >= 0 takes (row_tok, row_pos)[src[i]].
 void launch_rows_fill(int n, const int* src, int* tok, int* pos, const int* row_tok, const int* row_pos, hipStream_t st);
 void launch_beam_start(int n, const int* gs, const int* ws, int K, const int* win_prompt, int P, const int* win_slot,
                        int n_ctx, int* tokens, int* lin, int* seq_len, int* done, float* cum, int* hyp_slot, int* n_fin,
-                       hipStream_t st);
+                       hipStream_t st, const int* win_len = nullptr, const int* win_maxlen = nullptr,
+                       int* hyp_begin = nullptr, int* hyp_maxlen = nullptr);
+
+// dst[dst_row[i]][0..V) = src[i][0..V) for i < n (f32 rows; the ragged prefill's per-class logit rows -> selection order)
+void launch_rows_scatter(const float* src, float* dst, const int* dst_row, int n, int V, hipStream_t st);
 
 // one block per row (n_rows = hypotheses, or the compacted row set's rows with p.row_hyp)
 void launch_logits_select(const SearchParams& p, int n_rows, hipStream_t st);

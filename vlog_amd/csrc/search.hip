@@ -19,6 +19,13 @@
 //   repetition penalty p: every id in that history gets x < 0 ? x * p : x / p (timestamps included);
 //   no-repeat n-gram n: every id that would complete an n-gram already in that history is masked.
 // They live in their own instantiations (RULES): with both off the kernels launched are the ones without them.
+//
+// Ragged prompts (RAG): one wm_generate call may hold windows whose prompts differ in length and whose total length
+// limits differ.  The prompt length (p.sample_begin) and the limit (p.max_length) then come from per-hypothesis
+// tables in device memory (p.hyp_begin / p.hyp_maxlen, indexed like seq_len), which the host fills once (lockstep
+// decode) or hyp_start / beam_start fill when a slot takes a window (row-set decodes): kernel arguments never change,
+// so captured step graphs stay valid across refills.  RAG is a template parameter of both select kernels: a call
+// without the tables launches the same instantiations as before, unchanged.
 #include "search.h"
 #include <stdexcept>
 #include <string>
@@ -80,7 +87,7 @@ __device__ float block_sum(float v, float* sh) {
 // layout (id t -> word t % SB, bit t / SB) are filled by the history scan that already finds the last timestamp:
 // s_seen marks the ids of the generated history, s_ban the ids an n-gram repeat would complete.  Each thread then
 // reads its own two words once: the ban word joins `rule`, the seen word rescales the register-resident row.
-template <int MODE, bool REC, bool RULES>
+template <int MODE, bool REC, bool RULES, bool RAG>
 __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
   __shared__ unsigned long long s_seen[RULES ? SB : 1];
   __shared__ unsigned long long s_ban[RULES ? SB : 1];
@@ -93,6 +100,7 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
   const int h = p.row_hyp ? p.row_hyp[row] : row;
   if (p.done[h]) return;
   const int len = p.seq_len[h];
+  const int sample_begin = RAG ? p.hyp_begin[h] : p.sample_begin;       // this hypothesis' prompt length
   const int* seq = p.tokens + (long long)h * p.n_ctx;
   const int tb = p.ts_begin;
   // position of the last sampled timestamp: a block-wide max instead of a serial backward scan (a text-only
@@ -103,7 +111,7 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
     s_ban[tid] = 0;
   }
   __syncthreads();
-  for (int i = p.sample_begin + tid; i < len; i += SB) {
+  for (int i = sample_begin + tid; i < len; i += SB) {
     const int t = seq[i];
     if (t >= tb) atomicMax(&s_last_ts, i);
     if (RULES && t >= 0 && t < SB * 64) {
@@ -113,7 +121,7 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
       // seq[i] ends an n-gram of the history whose first n-1 tokens are the last n-1 generated: it may not follow them
       // again.  j = this token's index among the generated ones: its n-gram starts at j - (n-1) >= 0 (so the history
       // holds >= n tokens and every index below stays inside it).  n = 1 compares nothing: every generated id is banned.
-      const int n = p.no_repeat_ngram, j = i - p.sample_begin;
+      const int n = p.no_repeat_ngram, j = i - sample_begin;
       if (n > 0 && j >= n - 1) {
         bool same = true;
         for (int m = 1; m < n && same; ++m) same = seq[i - m] == seq[len - m];
@@ -123,7 +131,7 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
   }
   __syncthreads();
   if (tid == 0) {
-    const int ns = len - p.sample_begin;
+    const int ns = len - sample_begin;
     const int last = ns >= 1 ? seq[len - 1] : -1;
     const int last_ts = ns >= 1 && last >= tb;
     const int pen_ts = ns < 2 || seq[len - 2] >= tb;
@@ -213,7 +221,7 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
     if (MODE == 2) {
       // the decode step of this hypothesis = tokens it has sampled so far (equal to the host's step counter
       // for every live hypothesis; read from the device so a captured step graph replays unchanged)
-      const float key = x * p.inv_temperature + gumbel(p.seed, gkey, len - p.sample_begin, i);
+      const float key = x * p.inv_temperature + gumbel(p.seed, gkey, len - sample_begin, i);
       if (is_ts) {
         if (better(key, i, gs.v, gs.i)) { gs.v = key; gs.i = i; }
       } else {
@@ -239,7 +247,7 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
   // (the worker turns that into FAILED, worker/transcription.py:436-443).  All tested values are block-uniform.
   if (isnan(st) || isnan(ss) || (mt.v == -INFINITY && ms.v == -INFINITY)) {
     if (tid == 0) {
-      wm_report_error(p.err, (isnan(st) || isnan(ss)) ? WM_ERR_NONFINITE : WM_ERR_NO_TOKEN, h, len - p.sample_begin);
+      wm_report_error(p.err, (isnan(st) || isnan(ss)) ? WM_ERR_NONFINITE : WM_ERR_NO_TOKEN, h, len - sample_begin);
       if (MODE == 1) {
         for (int r = 0; r < p.topk; ++r) {
           p.cand_tok[(long long)h * p.topk + r] = -1;
@@ -460,14 +468,14 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
       p.seq_len[h] = len + 1;
       p.row_tok[row] = tok;
       p.row_pos[row] = len;
-      if (len + 1 >= p.max_length) fin = true;
+      if (len + 1 >= (RAG ? p.hyp_maxlen[h] : p.max_length)) fin = true;
     }
     if (fin) {
       p.done[h] = 1;
       atomicSub(p.n_active, 1);
       if (p.res_tok) {
         const int o = p.hyp_out[h];
-        p.res_len[o] = len + (tok == p.eot ? 0 : 1) - p.sample_begin;
+        p.res_len[o] = len + (tok == p.eot ? 0 : 1) - sample_begin;
         p.res_cum[o] = cum;
       }
     }
@@ -479,13 +487,13 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
     __syncthreads();
     if (s_fin) {
       const int o = p.hyp_out[h];
-      const int n = len + (tok == p.eot ? 0 : 1) - p.sample_begin;     // generated tokens, <|endoftext|> excluded
-      const int* src = p.tokens + (long long)h * p.n_ctx + p.sample_begin;
+      const int n = len + (tok == p.eot ? 0 : 1) - sample_begin;     // generated tokens, <|endoftext|> excluded
+      const int* src = p.tokens + (long long)h * p.n_ctx + sample_begin;
       for (int t = tid; t < n; t += SB) p.res_tok[(long long)o * p.n_ctx + t] = src[t];
       if (REC && p.tok_lp && p.res_lp) {
-        const int nr = len + 1 - p.sample_begin;                       // records up to position len
-        const float* a = p.tok_lp + (long long)h * p.n_ctx + p.sample_begin;
-        const float* b = p.tok_lp_other ? p.tok_lp_other + (long long)h * p.n_ctx + p.sample_begin : nullptr;
+        const int nr = len + 1 - sample_begin;                       // records up to position len
+        const float* a = p.tok_lp + (long long)h * p.n_ctx + sample_begin;
+        const float* b = p.tok_lp_other ? p.tok_lp_other + (long long)h * p.n_ctx + sample_begin : nullptr;
         for (int t = tid; t < nr; t += SB) {
           p.res_lp[(long long)o * p.n_ctx + t] = a[t];
           if (b && p.res_lp_other) p.res_lp_other[(long long)o * p.n_ctx + t] = b[t];
@@ -516,19 +524,28 @@ void launch_logits_select(const SearchParams& p, int n_rows, hipStream_t st) {
   if (!(p.rep_penalty > 0.f) || p.no_repeat_ngram < 0)
     throw std::runtime_error("logits_select: repetition penalty must be > 0 and the n-gram size >= 0");
   const bool rules = p.rep_penalty != 1.0f || p.no_repeat_ngram > 0;
+  if ((p.hyp_begin != nullptr) != (p.hyp_maxlen != nullptr))
+    throw std::runtime_error("logits_select: the per-hypothesis tables come as a pair");
+  const bool rag = p.hyp_begin != nullptr;
   const dim3 g(n_rows), b(SB);
+#define SEL_LAUNCH(MODE, REC, RULES)                                                                      \
+  do {                                                                                                    \
+    if (rag) hipLaunchKernelGGL((logits_select_kernel<MODE, REC, RULES, true>), g, b, 0, st, p);          \
+    else hipLaunchKernelGGL((logits_select_kernel<MODE, REC, RULES, false>), g, b, 0, st, p);             \
+  } while (0)
   switch ((rules ? 6 : 0) + p.mode * 2 + (rec ? 1 : 0)) {
-    case 0: hipLaunchKernelGGL((logits_select_kernel<0, false, false>), g, b, 0, st, p); break;
-    case 1: hipLaunchKernelGGL((logits_select_kernel<0, true, false>), g, b, 0, st, p); break;
-    case 2: case 3: hipLaunchKernelGGL((logits_select_kernel<1, false, false>), g, b, 0, st, p); break;
-    case 4: hipLaunchKernelGGL((logits_select_kernel<2, false, false>), g, b, 0, st, p); break;
-    case 5: hipLaunchKernelGGL((logits_select_kernel<2, true, false>), g, b, 0, st, p); break;
-    case 6: hipLaunchKernelGGL((logits_select_kernel<0, false, true>), g, b, 0, st, p); break;
-    case 7: hipLaunchKernelGGL((logits_select_kernel<0, true, true>), g, b, 0, st, p); break;
-    case 8: case 9: hipLaunchKernelGGL((logits_select_kernel<1, false, true>), g, b, 0, st, p); break;
-    case 10: hipLaunchKernelGGL((logits_select_kernel<2, false, true>), g, b, 0, st, p); break;
-    default: hipLaunchKernelGGL((logits_select_kernel<2, true, true>), g, b, 0, st, p); break;
+    case 0: SEL_LAUNCH(0, false, false); break;
+    case 1: SEL_LAUNCH(0, true, false); break;
+    case 2: case 3: SEL_LAUNCH(1, false, false); break;
+    case 4: SEL_LAUNCH(2, false, false); break;
+    case 5: SEL_LAUNCH(2, true, false); break;
+    case 6: SEL_LAUNCH(0, false, true); break;
+    case 7: SEL_LAUNCH(0, true, true); break;
+    case 8: case 9: SEL_LAUNCH(1, false, true); break;
+    case 10: SEL_LAUNCH(2, false, true); break;
+    default: SEL_LAUNCH(2, true, true); break;
   }
+#undef SEL_LAUNCH
   WM_LAUNCH_CHECK("logits_select_kernel");
 }
 
@@ -536,11 +553,21 @@ void launch_logits_select(const SearchParams& p, int n_rows, hipStream_t st) {
 __global__ __launch_bounds__(256) void hyp_start_kernel(const int* __restrict__ hs, const int* __restrict__ ws,
                                                         const int* __restrict__ win_prompt, int P,
                                                         const int* __restrict__ win_slot, int n_ctx, int* tokens,
-                                                        int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out) {
+                                                        int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out,
+                                                        const int* __restrict__ win_len,
+                                                        const int* __restrict__ win_maxlen, int* hyp_begin,
+                                                        int* hyp_maxlen) {
   const int h = hs[blockIdx.x], w = ws[blockIdx.x];
-  for (int p = threadIdx.x; p < P; p += blockDim.x) tokens[(long long)h * n_ctx + p] = win_prompt[(long long)w * P + p];
+  // ragged prompts: P is the row stride of win_prompt, the window's own length comes from win_len (the padding
+  // behind it is not read) and the slot's rows of the selection tables are filled here
+  const int n = win_len ? win_len[w] : P;
+  for (int p = threadIdx.x; p < n; p += blockDim.x) tokens[(long long)h * n_ctx + p] = win_prompt[(long long)w * P + p];
   if (threadIdx.x == 0) {
-    seq_len[h] = P;
+    if (win_len) {
+      hyp_begin[h] = n;
+      hyp_maxlen[h] = win_maxlen[w];
+    }
+    seq_len[h] = n;
     done[h] = 0;
     cum[h] = 0.f;
     hyp_slot[h] = win_slot[w];
@@ -549,10 +576,12 @@ __global__ __launch_bounds__(256) void hyp_start_kernel(const int* __restrict__ 
 }
 
 void launch_hyp_start(int n, const int* hs, const int* ws, const int* win_prompt, int P, const int* win_slot, int n_ctx,
-                      int* tokens, int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out, hipStream_t st) {
+                      int* tokens, int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out, hipStream_t st,
+                      const int* win_len, const int* win_maxlen, int* hyp_begin, int* hyp_maxlen) {
   if (n <= 0) return;
+  if (win_len && (!win_maxlen || !hyp_begin || !hyp_maxlen)) throw std::runtime_error("hyp_start: incomplete ragged tables");
   hipLaunchKernelGGL(hyp_start_kernel, dim3(n), dim3(64), 0, st, hs, ws, win_prompt, P, win_slot, n_ctx, tokens, seq_len,
-                     done, cum, hyp_slot, hyp_out);
+                     done, cum, hyp_slot, hyp_out, win_len, win_maxlen, hyp_begin, hyp_maxlen);
   WM_LAUNCH_CHECK("hyp_start_kernel");
 }
 
@@ -564,16 +593,23 @@ __global__ __launch_bounds__(256) void beam_start_kernel(const int* __restrict__
                                                          const int* __restrict__ win_prompt, int P,
                                                          const int* __restrict__ win_slot, int n_ctx, int* tokens,
                                                          int* lin, int* seq_len, int* done, float* cum, int* hyp_slot,
-                                                         int* n_fin) {
+                                                         int* n_fin, const int* __restrict__ win_len,
+                                                         const int* __restrict__ win_maxlen, int* hyp_begin,
+                                                         int* hyp_maxlen) {
   const int g = gs[blockIdx.x], w = ws[blockIdx.x], h0 = g * K;
-  for (int i = threadIdx.x; i < K * P; i += blockDim.x) {
-    const int b = i / P, p = i - b * P;
+  const int n = win_len ? win_len[w] : P;      // ragged prompts: as hyp_start_kernel
+  for (int i = threadIdx.x; i < K * n; i += blockDim.x) {
+    const int b = i / n, p = i - b * n;
     tokens[(long long)(h0 + b) * n_ctx + p] = win_prompt[(long long)w * P + p];
     lin[(long long)(h0 + b) * n_ctx + p] = h0;
   }
   if (threadIdx.x < K) {
     const int h = h0 + threadIdx.x;
-    seq_len[h] = P;
+    if (win_len) {
+      hyp_begin[h] = n;
+      hyp_maxlen[h] = win_maxlen[w];
+    }
+    seq_len[h] = n;
     done[h] = 0;
     cum[h] = threadIdx.x == 0 ? 0.f : -INFINITY;
     hyp_slot[h] = win_slot[w];
@@ -583,10 +619,11 @@ __global__ __launch_bounds__(256) void beam_start_kernel(const int* __restrict__
 
 void launch_beam_start(int n, const int* gs, const int* ws, int K, const int* win_prompt, int P, const int* win_slot,
                        int n_ctx, int* tokens, int* lin, int* seq_len, int* done, float* cum, int* hyp_slot, int* n_fin,
-                       hipStream_t st) {
+                       hipStream_t st, const int* win_len, const int* win_maxlen, int* hyp_begin, int* hyp_maxlen) {
   if (n <= 0) return;
+  if (win_len && (!win_maxlen || !hyp_begin || !hyp_maxlen)) throw std::runtime_error("beam_start: incomplete ragged tables");
   hipLaunchKernelGGL(beam_start_kernel, dim3(n), dim3(256), 0, st, gs, ws, K, win_prompt, P, win_slot, n_ctx, tokens,
-                     lin, seq_len, done, cum, hyp_slot, n_fin);
+                     lin, seq_len, done, cum, hyp_slot, n_fin, win_len, win_maxlen, hyp_begin, hyp_maxlen);
   WM_LAUNCH_CHECK("beam_start_kernel");
 }
 
@@ -608,6 +645,19 @@ void launch_rows_fill(int n, const int* src, int* tok, int* pos, const int* row_
   WM_LAUNCH_CHECK("rows_fill_kernel");
 }
 
+__global__ __launch_bounds__(256) void rows_scatter_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                           const int* __restrict__ dst_row, int V) {
+  const float* s = src + (long long)blockIdx.x * V;
+  float* d = dst + (long long)dst_row[blockIdx.x] * V;
+  for (int i = threadIdx.x; i < V; i += blockDim.x) d[i] = s[i];
+}
+
+void launch_rows_scatter(const float* src, float* dst, const int* dst_row, int n, int V, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(rows_scatter_kernel, dim3(n), dim3(256), 0, st, src, dst, dst_row, V);
+  WM_LAUNCH_CHECK("rows_scatter_kernel");
+}
+
 // ------------------------------------------------------------------------------------ beam bookkeeping
 #define BMAX 8
 #define CMAX 16
@@ -617,6 +667,7 @@ void launch_rows_fill(int n, const int* src, int* tok, int* pos, const int* row_
 // LDS, so the one serial walk (live beams / finished list, <= K (K+1) steps) touches no scratch memory; the
 // finished hypotheses' tokens are copied by the whole workgroup.  (The earlier form ran an insertion sort and
 // the copies in thread 0 over scratch arrays: ~0.2 ms per decode step of the sequential beam-5 call.)
+template <bool RAG>
 __global__ __launch_bounds__(256) void beam_select_kernel(BeamParams p) {
   constexpr int NC = BMAX * (BMAX + 1);
   __shared__ int s_tok[BMAX][448];
@@ -633,6 +684,9 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamParams p) {
   const int K = p.beam, h0 = w * K, T = K + 1, NK = K * T;
   if (p.done[h0]) return;
   const int len = p.seq_len[h0];
+  // the window's prompt length and length limit (RAG: from its first hypothesis' rows of the tables)
+  const int sample_begin = RAG ? p.hyp_begin[h0] : p.sample_begin;
+  const int max_length = RAG ? p.hyp_maxlen[h0] : p.max_length;
   const bool rec = p.tok_lp != nullptr;
   for (int i = tid; i < K * len; i += blockDim.x) {
     const int b = i / len, t = i - b * len;
@@ -687,7 +741,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamParams p) {
     p.n_fin[w] = nf;
     s_nlive = nlive;
     s_nf_new = nnew;
-    const bool fin = nf >= p.max_cand || len + 1 >= p.max_length || nlive == 0;
+    const bool fin = nf >= p.max_cand || len + 1 >= max_length || nlive == 0;
     if (fin) {
       for (int j = 0; j < K; ++j) p.done[h0 + j] = 1;
       atomicSub(p.n_active, K);
@@ -695,11 +749,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamParams p) {
   }
   __syncthreads();
   {
-    const int nnew = s_nf_new, ng = len - p.sample_begin;
+    const int nnew = s_nf_new, ng = len - sample_begin;
     for (int i = tid; i < nnew * ng; i += blockDim.x) {
       const int f = i / ng, t = i - f * ng;
-      p.fin_tok[((long long)w * p.max_cand + f_slot[f]) * p.n_ctx + t] = s_tok[f_src[f]][p.sample_begin + t];
-      if (rec) p.fin_lp[((long long)w * p.max_cand + f_slot[f]) * p.n_ctx + t] = s_lp[f_src[f]][p.sample_begin + t];
+      p.fin_tok[((long long)w * p.max_cand + f_slot[f]) * p.n_ctx + t] = s_tok[f_src[f]][sample_begin + t];
+      if (rec) p.fin_lp[((long long)w * p.max_cand + f_slot[f]) * p.n_ctx + t] = s_lp[f_src[f]][sample_begin + t];
     }
     if (tid < nnew) {
       p.fin_len[w * p.max_cand + f_slot[tid]] = ng;
@@ -735,7 +789,10 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamParams p) {
 void launch_beam_select(const BeamParams& p, int n_win, hipStream_t st) {
   if (n_win <= 0) return;
   if (p.beam > BMAX || p.max_cand > CMAX || p.n_ctx > 448) throw std::runtime_error("beam_select: limits exceeded");
-  hipLaunchKernelGGL(beam_select_kernel, dim3(n_win), dim3(256), 0, st, p);
+  if ((p.hyp_begin != nullptr) != (p.hyp_maxlen != nullptr))
+    throw std::runtime_error("beam_select: the per-hypothesis tables come as a pair");
+  if (p.hyp_begin) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(n_win), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(n_win), dim3(256), 0, st, p);
   WM_LAUNCH_CHECK("beam_select_kernel");
 }
 

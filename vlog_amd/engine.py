@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -292,28 +292,65 @@ class GpuEngine:
             _capi.check(self.lib.wm_cross_kv(self.h, C.c_void_p(enc.data_ptr()), B, slot0, self.stream_ptr()), "wm_cross_kv")
 
     def generate(self, slots: Sequence[int], prompts: Sequence[Sequence[int]], *, beam_size: int = 1,
-                 patience: float = 1.0, length_penalty: float = 1.0, max_length: int = 448,
+                 patience: float = 1.0, length_penalty: float = 1.0, max_length: Union[int, Sequence[int]] = 448,
                  temperature: float = 0.0, num_hypotheses: int = 1, seed: int = 0,
                  suppress_tokens: Sequence[int] = (), suppress_blank: bool = True,
                  max_initial_timestamp_index: Optional[int] = 50, with_timestamps: bool = True,
-                 sot_index: Optional[int] = None, check_every: int = 4, max_rows: int = 0, compact: bool = False,
-                 record_logprobs: bool = False, stats: Optional[dict] = None, repetition_penalty: float = 1.0,
-                 no_repeat_ngram_size: int = 0) -> Tuple[List[GenResult], int]:
+                 sot_index: Union[None, int, Sequence[int]] = None, check_every: int = 4, max_rows: int = 0,
+                 compact: bool = False, record_logprobs: bool = False, stats: Optional[dict] = None,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                 prompt_lens: Optional[Sequence[int]] = None) -> Tuple[List[GenResult], int]:
         """ctranslate2 Whisper.generate over windows in slots (wm_generate).  max_rows / compact: the row-set decode
         (greedy / one sampled hypothesis; windows refill finished rows in the given order, include/whisper_mi355.h);
         beam search with compact drops finished windows' hypotheses from the passes.
         record_logprobs: per-step log-prob records in each GenResult.  stats: filled with the decode's counters.
         repetition_penalty / no_repeat_ngram_size: CTranslate2's two logit rules over each hypothesis' generated tokens,
-        applied on the device before every other rule (1.0 and 0: off; a negative value raises RuntimeError)."""
+        applied on the device before every other rule (1.0 and 0: off; a negative value raises RuntimeError).
+        Ragged prompts (ABI 4): the prompts may differ in length (they are padded to the longest and the lengths passed
+        on); sot_index=None then derives one index per prompt, and max_length may be one total length per window
+        (prompt included).  prompt_lens: the prompts are rows of one length already and window w's prompt is the first
+        prompt_lens[w] tokens of its row (the padding is passed as it is: the engine neither reads nor validates it).
+        A call whose prompts share one length, with an int max_length and sot_index and no prompt_lens, builds the
+        one-length arguments (NULL for the three per-window pointers)."""
         W = len(slots)
-        P = len(prompts[0])
-        if any(len(p) != P for p in prompts):
-            raise ValueError("all prompts of one generate call must have the same length")
         st = self.dims.specials
-        if sot_index is None:
-            sot_index = list(prompts[0]).index(st.sot) if st.sot in prompts[0] else -1
+        if prompt_lens is not None:
+            lens_in = [int(n) for n in prompt_lens]
+            P = len(prompts[0])
+            if len(lens_in) != W or any(len(p) != P for p in prompts):
+                raise ValueError("prompt_lens needs one length per window and prompts padded to one row length")
+        else:
+            lens_in = [len(p) for p in prompts]
+            P = max(lens_in)
+        per_ml = not isinstance(max_length, (int, np.integer))
+        per_sot = sot_index is not None and not isinstance(sot_index, (int, np.integer))
+        ragged = prompt_lens is not None or any(n != P for n in lens_in) or per_ml or per_sot
+        ml_in = [int(v) for v in max_length] if per_ml else [int(max_length)] * W
+        if len(ml_in) != W:
+            raise ValueError("max_length needs one value per window")
+        max_length = max(ml_in)                  # the stride of the output rows
         h_slots = np.ascontiguousarray(slots, dtype=np.int32)
-        h_prompts = np.ascontiguousarray(np.asarray(prompts, dtype=np.int32).reshape(W, P))
+        h_lens = h_sots = h_mls = None
+        if not ragged:
+            if sot_index is None:
+                sot_index = list(prompts[0]).index(st.sot) if st.sot in prompts[0] else -1
+            h_prompts = np.ascontiguousarray(np.asarray(prompts, dtype=np.int32).reshape(W, P))
+        else:
+            h_prompts = np.full((W, P), -1, dtype=np.int32)      # the padding is no token: the engine never reads it
+            for w, p in enumerate(prompts):
+                h_prompts[w, :len(p)] = np.asarray(p, dtype=np.int32)
+            if sot_index is None:
+                sots = [list(p[:n]).index(st.sot) if st.sot in list(p[:n]) else -1 for p, n in zip(prompts, lens_in)]
+            elif per_sot:
+                sots = [int(v) for v in sot_index]
+                if len(sots) != W:
+                    raise ValueError("sot_index needs one value per window")
+            else:
+                sots = [int(sot_index)] * W
+            h_lens = np.ascontiguousarray(lens_in, dtype=np.int32)
+            h_sots = np.ascontiguousarray(sots, dtype=np.int32)
+            h_mls = np.ascontiguousarray(ml_in, dtype=np.int32)
+            sot_index = int(sots[0])
         sup = np.ascontiguousarray(sorted(set(int(t) for t in suppress_tokens)), dtype=np.int32)
         if sup.size == 0:
             sup = np.zeros(1, dtype=np.int32) - 1
@@ -333,7 +370,8 @@ class GpuEngine:
             check_every, _i32p(toks), _i32p(lens), _f32p(scores), _f32p(cum), _f32p(ns), _i32p(steps),
             int(max_rows), int(bool(compact)), _f32p(lp) if lp is not None else None,
             _f32p(lpo) if lpo is not None else None, st64.ctypes.data_as(C.POINTER(C.c_int64)),
-            float(repetition_penalty), int(no_repeat_ngram_size))
+            float(repetition_penalty), int(no_repeat_ngram_size),
+            _i32p(h_lens) if ragged else None, _i32p(h_sots) if ragged else None, _i32p(h_mls) if ragged else None)
         with torch.cuda.device(self.device):
             _capi.check(self.lib.wm_generate(self.h, C.byref(a), self.stream_ptr()), "wm_generate")
         res = []
@@ -341,7 +379,7 @@ class GpuEngine:
             n = int(lens[w])
             r = GenResult(toks[w, :n].tolist(), float(scores[w]), float(cum[w]), float(ns[w]))
             if lp is not None:
-                nr = min(max_length, n + (1 if P + n < max_length else 0))
+                nr = min(max_length, n + (1 if lens_in[w] + n < ml_in[w] else 0))
                 r.token_logprobs = lp[w, :nr].copy()
                 r.token_logprobs_other = lpo[w, :nr].copy()
             res.append(r)

@@ -1,0 +1,238 @@
+"""The sequential (parity) mode's host state, one object per file, and the lockstep scheduler over several files.
+
+faster-whisper `generate_segments` [FW↑ 1.1.x] is a loop over one file: seek position, clip list, previous-text
+prompt, temperature fallback, segment split, word alignment.  Here the loop's body is an object with two operations,
+so that one driver can hold several files and decode the next window of each in shared decoder passes
+(`WhisperModel.transcribe_many`), while `WhisperModel.generate_segments` stays the one-file driver:
+
+  SeekState.next_request() -> the next window to decode (seek, size, prompt, seed base), or None at the file's end
+  SeekState.consume(...)   -> takes the window's decode result, returns the segments to yield
+
+Nothing here touches the GPU (no torch import): the decode, the fallback passes and the alignment are callables the
+driver supplies, so tests run both the state and the scheduler against a scripted backend.
+"""
+from __future__ import annotations
+
+from collections import deque
+from dataclasses import dataclass
+from typing import Callable, Iterable, List, Optional, Sequence, Tuple
+
+from . import segments as segs
+from .dims import HOP_LENGTH, N_FRAMES, SAMPLE_RATE
+
+FRAMES_PER_SECOND = SAMPLE_RATE // HOP_LENGTH
+
+
+@dataclass
+class WindowRequest:
+    window: int            # the file's window counter: the seed of temperature i is window + i
+    seek: int
+    size: int              # mel frames of the window
+    time_offset: float
+    duration: float
+    prompt: List[int]
+    max_length: int        # total decoder length of this window, prompt included
+
+
+def window_max_length(prompt: Sequence[int], max_new_tokens: Optional[int], model_max_length: int) -> int:
+    """faster-whisper generate_with_fallback's max_length: len(prompt) + max_new_tokens, within the model's."""
+    max_length = len(prompt) + max_new_tokens if max_new_tokens is not None else model_max_length
+    if max_length > model_max_length:
+        raise ValueError(f"the length of the prompt is {len(prompt)}, and the max_new_tokens {max_length - len(prompt)}. "
+                         f"Thus, the combined length of the prompt and max_new_tokens is: {max_length}. This exceeds "
+                         f"the max_length of the Whisper model: {model_max_length}.")
+    return max_length
+
+
+def fallback_ladder(generate: Callable[[float, int], object], decode_text: Callable[[Sequence[int]], str], options,
+                    seed: int = 0, first=None):
+    """faster-whisper generate_with_fallback -> (result, avg_logprob, temperature, compression_ratio).
+    generate(temperature, seed) -> an object with tokens / score / no_speech_prob; temperature i runs with seed + i.
+    `first`: the result at temperatures[0] when a shared pass already computed it (the ladder then starts by judging
+    it, and calls generate only for the temperatures after it)."""
+    all_results, below_cr = [], []
+    decode_result = None
+    temperature = options.temperatures[0] if options.temperatures else 0.0
+    for i, temperature in enumerate(options.temperatures):
+        result = first if (i == 0 and first is not None) else generate(temperature, seed + i)
+        n = len(result.tokens)
+        avg_lp = segs.avg_logprob(result.score, n, options.length_penalty)
+        text = decode_text(result.tokens).strip()
+        cr = segs.compression_ratio(text)
+        decode_result = (result, avg_lp, temperature, cr)
+        all_results.append(decode_result)
+        fb, below = segs.needs_fallback(cr, avg_lp, result.no_speech_prob, options.compression_ratio_threshold,
+                                        options.log_prob_threshold, options.no_speech_threshold)
+        if below:
+            below_cr.append(decode_result)
+        if not fb:
+            break
+    else:
+        best = max(below_cr or all_results, key=lambda x: x[1])
+        decode_result = (best[0], best[1], temperature, best[3])
+    return decode_result
+
+
+def _get_end(segments: List[dict]) -> Optional[float]:
+    return next((w["end"] for s in reversed(segments) for w in reversed(s.get("words") or [])),
+                segments[-1]["end"] if segments else None)
+
+
+class SeekState:
+    """One file's position in the sequential mode: seek, clips, previous text, window counter, segment id."""
+
+    def __init__(self, content_frames: int, tokenizer, options, model_max_length: int = 448,
+                 frames_per_second: int = FRAMES_PER_SECOND):
+        self.content_frames = content_frames
+        self.tokenizer = tokenizer
+        self.options = options
+        self.model_max_length = model_max_length
+        self.frames_per_second = frames_per_second
+        ct = options.clip_timestamps
+        if isinstance(ct, str):
+            ct = [float(t) for t in (ct.split(",") if ct else [])]
+        seek_points = [round(t * frames_per_second) for t in ct]
+        if not seek_points:
+            seek_points.append(0)
+        if len(seek_points) % 2 == 1:
+            seek_points.append(content_frames)
+        self.seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
+        self.idx = 0                    # id of the last segment yielded
+        self.clip_idx = 0
+        self.seek = self.seek_clips[0][0]
+        self.all_tokens: List[int] = []
+        self.prompt_reset_since = 0
+        if options.initial_prompt is not None:
+            if isinstance(options.initial_prompt, str):
+                self.all_tokens.extend(tokenizer.encode(" " + options.initial_prompt.strip()))
+            else:
+                self.all_tokens.extend(options.initial_prompt)
+        self.last_speech_timestamp = 0.0
+        self.window = 0
+        self._request: Optional[WindowRequest] = None
+
+    def next_request(self) -> Optional[WindowRequest]:
+        """The window to decode next (the same object until it is consumed), or None when the file is done."""
+        if self._request is not None:
+            return self._request
+        o, tk = self.options, self.tokenizer
+        while self.clip_idx < len(self.seek_clips):
+            clip_start, clip_end = self.seek_clips[self.clip_idx]
+            clip_end = min(clip_end, self.content_frames)
+            if self.seek < clip_start:
+                self.seek = clip_start
+            if self.seek >= clip_end:
+                self.clip_idx += 1
+                if self.clip_idx < len(self.seek_clips):
+                    self.seek = self.seek_clips[self.clip_idx][0]
+                continue
+            seek = self.seek
+            size = min(N_FRAMES, self.content_frames - seek, clip_end - seek)
+            prompt = segs.build_prompt(tk.encode, tk.sot_sequence, tk.sot_prev, tk.no_timestamps, tk.timestamp_begin,
+                                       self.model_max_length, self.all_tokens[self.prompt_reset_since:],
+                                       o.without_timestamps, prefix=o.prefix if seek == 0 else None, hotwords=o.hotwords)
+            self._request = WindowRequest(window=self.window, seek=seek, size=size,
+                                          time_offset=seek * HOP_LENGTH / SAMPLE_RATE,
+                                          duration=size * HOP_LENGTH / SAMPLE_RATE, prompt=prompt,
+                                          max_length=window_max_length(prompt, o.max_new_tokens, self.model_max_length))
+            return self._request
+        return None
+
+    def consume(self, decode_result: Tuple[object, float, float, float],
+                align: Optional[Callable[[List[dict], int, float], float]] = None) -> List[dict]:
+        """Takes the pending window's (result, avg_logprob, temperature, compression_ratio) and returns the segments
+        to yield, as dicts with the fields of `Segment` (words: the aligned word dicts or None).
+        align(current_segments, segment_size, last_speech_timestamp) -> last_speech_timestamp adds the word times in
+        place (word_timestamps; it runs before the seek position is final, which depends on the last word's end)."""
+        req = self._request
+        if req is None:
+            raise RuntimeError("SeekState.consume without a pending request")
+        self._request = None
+        o, tk = self.options, self.tokenizer
+        result, avg_lp, temperature, cr = decode_result
+        self.window += 1
+        if segs.should_skip_window(result.no_speech_prob, avg_lp, o.no_speech_threshold, o.log_prob_threshold):
+            self.seek += req.size
+            return []
+        previous_seek = req.seek
+        current, self.seek, single_ending = segs.split_segments_by_timestamps(
+            result.tokens, tk.timestamp_begin, req.time_offset, req.size, req.duration, req.seek)
+        if o.word_timestamps:
+            self.last_speech_timestamp = align(current, req.size, self.last_speech_timestamp)
+            if not single_ending:
+                last_word_end = _get_end(current)
+                if last_word_end is not None and last_word_end > req.time_offset:
+                    self.seek = round(last_word_end * self.frames_per_second)
+        out = []
+        for s in current:
+            text = tk.decode(s["tokens"])
+            if s["start"] == s["end"] or not text.strip():
+                continue
+            self.all_tokens.extend(s["tokens"])
+            self.idx += 1
+            out.append(dict(id=self.idx, seek=previous_seek, start=s["start"], end=s["end"], text=text, tokens=s["tokens"],
+                            temperature=temperature, avg_logprob=avg_lp, compression_ratio=cr,
+                            no_speech_prob=result.no_speech_prob, words=s["words"] if o.word_timestamps else None))
+        if not o.condition_on_previous_text or temperature > o.prompt_reset_on_temperature:
+            self.prompt_reset_since = len(self.all_tokens)
+        return out
+
+
+def run_lockstep(n_files: int, max_files: int, open_file: Callable[[int], SeekState],
+                 decode_round: Callable[[List[Tuple[int, SeekState, WindowRequest]]], None],
+                 close_file: Optional[Callable[[int], None]] = None) -> int:
+    """Decodes n_files files with at most max_files in flight.  Each round takes the next window of every file in
+    flight, in the order the files entered (entry i of the round is cross slot i), and hands them to
+    decode_round([(file, state, request)]), which must consume every request.  When a file ends, the next pending
+    file takes its place in the following round; close_file(file) is called once a file has no window left (the
+    driver drops what it held for it).  -> the number of rounds."""
+    if max_files < 1:
+        raise ValueError("max_files must be >= 1")
+    pending = deque(range(n_files))
+    active: List[Tuple[int, SeekState]] = []
+    rounds = 0
+    while pending or active:
+        batch: List[Tuple[int, SeekState, WindowRequest]] = []
+        keep: List[Tuple[int, SeekState]] = []
+        for f, state in active:
+            req = state.next_request()
+            if req is not None:
+                batch.append((f, state, req))
+                keep.append((f, state))
+            elif close_file is not None:
+                close_file(f)
+        while pending and len(keep) < max_files:
+            f = pending.popleft()
+            state = open_file(f)
+            req = state.next_request()
+            if req is not None:                 # (an empty file never enters a round)
+                batch.append((f, state, req))
+                keep.append((f, state))
+            elif close_file is not None:
+                close_file(f)
+        active = keep
+        if not batch:
+            continue
+        decode_round(batch)
+        for _, state, _ in batch:
+            if state._request is not None:
+                raise RuntimeError("run_lockstep: decode_round left a request unconsumed")
+        rounds += 1
+    return rounds
+
+
+def decode_round_with(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
+                      first_pass: Callable[[List[int]], List[object]],
+                      fallback_generate: Callable[[int, float, int], object],
+                      align: Optional[Callable[[int, List[dict], int, float], float]],
+                      emit: Callable[[int, List[dict]], None]) -> None:
+    """One lockstep round over `batch` (entry i = cross slot i).
+    first_pass(indices) -> the results at temperatures[0] of those entries, decoded together (the caller may split
+    them further, e.g. by suppress list); fallback_generate(i, temperature, seed) re-decodes entry i alone, for the
+    temperatures after the first; align(i, segments, size, last_speech) word-aligns entry i against its own slot;
+    emit(file, segments) receives each file's new segments."""
+    firsts = first_pass(list(range(len(batch))))
+    for i, (f, state, req) in enumerate(batch):
+        decode = fallback_ladder(lambda t, seed, i=i: fallback_generate(i, t, seed), state.tokenizer.decode, state.options,
+                                 seed=req.window, first=firsts[i])
+        emit(f, state.consume(decode, (lambda cur, size, last, i=i: align(i, cur, size, last)) if align else None))

@@ -35,6 +35,7 @@ import torch
 
 from . import segments as segs
 from .audio import load_audio
+from .seek_state import SeekState, decode_round_with, fallback_ladder, run_lockstep, window_max_length
 from .dims import CHUNK_LENGTH, HOP_LENGTH, N_FRAMES, SAMPLE_RATE, TIME_PRECISION
 from .tokenizer import Tokenizer
 from .weights import resolve_model
@@ -319,6 +320,36 @@ class WhisperModel:
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
                 language_detection_segments=language_detection_segments)
+        features, tokenizer, options, info, speech_chunks = self._prepare_file(
+            audio, language=language, task=task, beam_size=beam_size, best_of=best_of, patience=patience,
+            length_penalty=length_penalty, repetition_penalty=repetition_penalty,
+            no_repeat_ngram_size=no_repeat_ngram_size, temperature=temperature,
+            compression_ratio_threshold=compression_ratio_threshold, log_prob_threshold=log_prob_threshold,
+            no_speech_threshold=no_speech_threshold, condition_on_previous_text=condition_on_previous_text,
+            prompt_reset_on_temperature=prompt_reset_on_temperature, initial_prompt=initial_prompt, prefix=prefix,
+            suppress_blank=suppress_blank, suppress_tokens=suppress_tokens, without_timestamps=without_timestamps,
+            max_initial_timestamp=max_initial_timestamp, word_timestamps=word_timestamps,
+            prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
+            multilingual=multilingual, vad_filter=vad_filter, vad_parameters=vad_parameters,
+            max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
+            hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hotwords,
+            language_detection_threshold=language_detection_threshold,
+            language_detection_segments=language_detection_segments)
+        gen = self.generate_segments(features, tokenizer, options)
+        if speech_chunks:
+            from .vad import restore_speech_timestamps
+            gen = restore_speech_timestamps(gen, speech_chunks, SAMPLE_RATE)
+        return gen, info
+
+    def _prepare_file(self, audio, *, language, task, beam_size, best_of, patience, length_penalty, repetition_penalty,
+                      no_repeat_ngram_size, temperature, compression_ratio_threshold, log_prob_threshold,
+                      no_speech_threshold, condition_on_previous_text, prompt_reset_on_temperature, initial_prompt,
+                      prefix, suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp,
+                      word_timestamps, prepend_punctuations, append_punctuations, multilingual, vad_filter,
+                      vad_parameters, max_new_tokens, clip_timestamps, hallucination_silence_threshold, hotwords,
+                      language_detection_threshold, language_detection_segments):
+        """What `transcribe` does for one file before its seek loop: load, VAD, log-mel, language, tokenizer, options.
+        -> (features, tokenizer, options, info, speech_chunks)"""
         if not isinstance(audio, np.ndarray):
             audio = load_audio(audio)
         audio = np.asarray(audio, dtype=np.float32)
@@ -363,14 +394,10 @@ class WhisperModel:
             append_punctuations=append_punctuations, multilingual=multilingual, max_new_tokens=max_new_tokens,
             clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
             hotwords=hotwords)
-        gen = self.generate_segments(features, tokenizer, options)
-        if speech_chunks:
-            from .vad import restore_speech_timestamps
-            gen = restore_speech_timestamps(gen, speech_chunks, SAMPLE_RATE)
         info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
                                  duration_after_vad=duration_after_vad, all_language_probs=all_language_probs,
                                  transcription_options=options, vad_options=vad_opts)
-        return gen, info
+        return features, tokenizer, options, info, speech_chunks
 
     # ------------------------------------------------------------------ prompt / generate
     def get_prompt(self, tokenizer: Tokenizer, previous_tokens: List[int], without_timestamps: bool = False,
@@ -380,12 +407,12 @@ class WhisperModel:
                                  prefix, hotwords)
 
     def _generate(self, prompt: List[int], options: TranscriptionOptions, temperature: float, max_length: int,
-                  seed: int) -> _GenOut:
+                  seed: int, slot: int = 0) -> _GenOut:
         st = self.dims.specials
         mit = int(round(options.max_initial_timestamp / self.time_precision))
         sampling = temperature > 0
         res, _ = self.engine.generate(
-            [0], [prompt], beam_size=1 if sampling else options.beam_size, patience=options.patience,
+            [slot], [prompt], beam_size=1 if sampling else options.beam_size, patience=options.patience,
             length_penalty=options.length_penalty, max_length=max_length, temperature=temperature,
             num_hypotheses=options.best_of if sampling else 1, seed=seed, suppress_tokens=options.suppress_tokens,
             suppress_blank=options.suppress_blank, max_initial_timestamp_index=mit,
@@ -396,115 +423,212 @@ class WhisperModel:
         return _GenOut(r.tokens, r.score, r.no_speech_prob)
 
     def generate_with_fallback(self, prompt: List[int], tokenizer: Tokenizer, options: TranscriptionOptions,
-                               seed: int = 0):
-        """faster-whisper generate_with_fallback -> (result, avg_logprob, temperature, compression_ratio)."""
-        all_results, below_cr = [], []
-        if options.max_new_tokens is not None:
-            max_length = len(prompt) + options.max_new_tokens
-        else:
-            max_length = self.max_length
-        if max_length > self.max_length:
-            raise ValueError(f"the length of the prompt is {len(prompt)}, and the max_new_tokens {max_length - len(prompt)}. "
-                             f"Thus, the combined length of the prompt and max_new_tokens is: {max_length}. This exceeds "
-                             f"the max_length of the Whisper model: {self.max_length}.")
-        decode_result = None
-        temperature = options.temperatures[0] if options.temperatures else 0.0
-        for i, temperature in enumerate(options.temperatures):
-            result = self._generate(prompt, options, temperature, max_length, seed + i)
-            n = len(result.tokens)
-            avg_lp = segs.avg_logprob(result.score, n, options.length_penalty)
-            text = tokenizer.decode(result.tokens).strip()
-            cr = segs.compression_ratio(text)
-            decode_result = (result, avg_lp, temperature, cr)
-            all_results.append(decode_result)
-            fb, below = segs.needs_fallback(cr, avg_lp, result.no_speech_prob, options.compression_ratio_threshold,
-                                            options.log_prob_threshold, options.no_speech_threshold)
-            if below:
-                below_cr.append(decode_result)
-            if not fb:
-                break
-        else:
-            best = max(below_cr or all_results, key=lambda x: x[1])
-            decode_result = (best[0], best[1], temperature, best[3])
-        return decode_result
+                               seed: int = 0, slot: int = 0, first: Optional[_GenOut] = None):
+        """faster-whisper generate_with_fallback -> (result, avg_logprob, temperature, compression_ratio), decoding
+        against the window in cross slot `slot`.  `first`: the result at temperatures[0] when a shared pass already
+        computed it (transcribe_many); the ladder then only runs the temperatures after it."""
+        max_length = window_max_length(prompt, options.max_new_tokens, self.max_length)
+        return fallback_ladder(lambda t, sd: self._generate(prompt, options, t, max_length, sd, slot), tokenizer.decode,
+                               options, seed=seed, first=first)
 
     # ------------------------------------------------------------------ seek loop
+    def _segment(self, d: dict) -> Segment:
+        words = d.pop("words")
+        return Segment(words=[Word(**w) for w in words] if words is not None else None, **d)
+
     def generate_segments(self, features: torch.Tensor, tokenizer: Tokenizer, options: TranscriptionOptions):
-        content_frames = features.shape[1] - 1
-        ct = options.clip_timestamps
-        if isinstance(ct, str):
-            ct = [float(t) for t in (ct.split(",") if ct else [])]
-        seek_points = [round(t * self.frames_per_second) for t in ct]
-        if not seek_points:
-            seek_points.append(0)
-        if len(seek_points) % 2 == 1:
-            seek_points.append(content_frames)
-        seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
-        idx = 0
-        clip_idx = 0
-        seek = seek_clips[0][0]
-        all_tokens: List[int] = []
-        prompt_reset_since = 0
-        if options.initial_prompt is not None:
-            if isinstance(options.initial_prompt, str):
-                all_tokens.extend(tokenizer.encode(" " + options.initial_prompt.strip()))
-            else:
-                all_tokens.extend(options.initial_prompt)
-        last_speech_timestamp = 0.0
-        window = 0
-        while clip_idx < len(seek_clips):
-            clip_start, clip_end = seek_clips[clip_idx]
-            clip_end = min(clip_end, content_frames)
-            if seek < clip_start:
-                seek = clip_start
-            if seek >= clip_end:
-                clip_idx += 1
-                if clip_idx < len(seek_clips):
-                    seek = seek_clips[clip_idx][0]
-                continue
-            time_offset = seek * HOP_LENGTH / SAMPLE_RATE
-            segment_size = min(N_FRAMES, content_frames - seek, clip_end - seek)
-            segment_duration = segment_size * HOP_LENGTH / SAMPLE_RATE
-            previous_tokens = all_tokens[prompt_reset_since:]
+        """The one-file driver of vlog_amd/seek_state.py SeekState (faster-whisper generate_segments)."""
+        state = SeekState(features.shape[1] - 1, tokenizer, options, self.max_length, self.frames_per_second)
+        while True:
+            req = state.next_request()
+            if req is None:
+                return
             # one lock scope from the encode to the word alignment: the alignment reads the window's encoder
             # output from slot 0, which another thread's transcribe must not replace in between
             with self._lock:
                 self._use_cross_form(options.beam_size)
-                self._encode(features, seek, segment_size, 0)
-                prompt = self.get_prompt(tokenizer, previous_tokens, options.without_timestamps,
-                                         prefix=options.prefix if seek == 0 else None, hotwords=options.hotwords)
-                result, avg_lp, temperature, cr = self.generate_with_fallback(prompt, tokenizer, options, seed=window)
-                skip = segs.should_skip_window(result.no_speech_prob, avg_lp, options.no_speech_threshold,
-                                               options.log_prob_threshold)
-                if not skip:
-                    previous_seek = seek
-                    current, seek, single_ending = segs.split_segments_by_timestamps(
-                        result.tokens, tokenizer.timestamp_begin, time_offset, segment_size, segment_duration, seek)
-                    if options.word_timestamps:
-                        last_speech_timestamp = self.add_word_timestamps(
-                            [current], tokenizer, segment_size, options.prepend_punctuations,
-                            options.append_punctuations, last_speech_timestamp)
-            window += 1
-            if skip:
-                seek += segment_size
-                continue
-            if options.word_timestamps:
-                if not single_ending:
-                    last_word_end = _get_end(current)
-                    if last_word_end is not None and last_word_end > time_offset:
-                        seek = round(last_word_end * self.frames_per_second)
-            for s in current:
-                text = tokenizer.decode(s["tokens"])
-                if s["start"] == s["end"] or not text.strip():
-                    continue
-                all_tokens.extend(s["tokens"])
-                idx += 1
-                yield Segment(id=idx, seek=previous_seek, start=s["start"], end=s["end"], text=text,
-                              tokens=s["tokens"], temperature=temperature, avg_logprob=avg_lp, compression_ratio=cr,
-                              no_speech_prob=result.no_speech_prob,
-                              words=[Word(**w) for w in s["words"]] if options.word_timestamps else None)
-            if not options.condition_on_previous_text or temperature > options.prompt_reset_on_temperature:
-                prompt_reset_since = len(all_tokens)
+                self._encode(features, req.seek, req.size, 0)
+                decode = self.generate_with_fallback(req.prompt, tokenizer, options, seed=req.window)
+                out = state.consume(decode, lambda current, size, last: self.add_word_timestamps(
+                    [current], tokenizer, size, options.prepend_punctuations, options.append_punctuations, last))
+            for d in out:
+                yield self._segment(d)
+
+    def transcribe_many(self, audios: Sequence[Union[str, BinaryIO, np.ndarray]],
+                        language: Union[None, str, Sequence[Optional[str]]] = None, task: str = "transcribe",
+                        log_progress: bool = False, beam_size: int = 5, best_of: int = 5, patience: float = 1,
+                        length_penalty: float = 1, repetition_penalty: float = 1, no_repeat_ngram_size: int = 0,
+                        temperature: Union[float, List[float], Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+                        compression_ratio_threshold: Optional[float] = 2.4, log_prob_threshold: Optional[float] = -1.0,
+                        no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = True,
+                        prompt_reset_on_temperature: float = 0.5, initial_prompt=None, prefix=None,
+                        suppress_blank: bool = True, suppress_tokens: Optional[List[int]] = [-1],
+                        without_timestamps: bool = False, max_initial_timestamp: float = 1.0,
+                        word_timestamps: bool = False, prepend_punctuations: str = "\"'“¿([{-",
+                        append_punctuations: str = "\"'.。,，!！?？:：”)]}、", multilingual: bool = False,
+                        vad_filter: bool = False, vad_parameters=None, max_new_tokens: Optional[int] = None,
+                        chunk_length: Optional[int] = None, clip_timestamps: Union[str, List[float]] = "0",
+                        hallucination_silence_threshold: Optional[float] = None, hotwords=None,
+                        language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
+                        max_files: int = 16):
+        """`transcribe` for several files at once in the sequential (parity) mode -> [(list_of_segments, info)] in
+        input order; each file gets what `transcribe(file, same arguments)` gives for it alone.
+
+        The files decode in lockstep: each round takes the next 30 s window of every file in flight (at most
+        `max_files`; when a file ends the next pending one takes its place), encodes them in one call, and decodes
+        them in ONE ragged `engine.generate` at temperatures[0] (rows = files x beam), every file with its own seek
+        position and previous-text prompt.  The sequential decode is launch-bound at one file's few rows (DESIGN.md
+        §10.5), so the extra files' rows ride along in the same decoder passes.  A window that needs a fallback
+        temperature is re-decoded alone, with the calls `generate_with_fallback` makes (same seeds, same best_of);
+        word timestamps are aligned per file against its own slot.  language / initial_prompt / hotwords / prefix take
+        one value, or a list / tuple with one value per file (pass token ids of ONE initial prompt as a numpy array or
+        repeat them per file).  Files of different languages share rounds (the prompt carries the language); files whose
+        suppress lists differ are decoded in separate generate calls of the round.
+        max_files: files in flight.  Measured on one MI355X (large-v3 margin weights, the worker's call on 5-minute
+        clips, tools/bench_worker_call.py --files, profiles/worker_call_many.jsonl): files in flight -> RTFx summed
+        over the files / ms per decoder pass: 1 -> 133 / 2.10, 2 -> 240 / 2.31, 4 -> 365 / 3.03, 8 -> 593 / 3.64,
+        16 -> 924 / 4.45, 32 -> 1379 / 5.56.  The curve has no sharp knee: a pass never costs twice what half the rows
+        cost, so every doubling still pays (x1.80, 1.52, 1.62, 1.56, 1.49), while each file's own latency grows (2.3 s
+        alone, 5.2 s at 16, 7.0 s at 32 for a 5-minute clip).  The default is the last doubling that gains at least
+        x1.5 (the 16-files line); a worker that only wants throughput can pass 32.
+        With throughput mode on, this is BatchedInferencePipeline.transcribe_many."""
+        for name, val, default in (("multilingual", multilingual, False),
+                                   ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
+            if val != default:
+                raise NotImplementedError(f"{name}={val!r} is not supported by the MI355X engine")
+        if chunk_length not in (None, CHUNK_LENGTH):
+            raise NotImplementedError("chunk_length other than 30 s is not supported")
+        if task not in ("transcribe", "translate"):
+            raise ValueError(f"unknown task {task!r}")
+        n = len(audios)
+        if max_files < 1:
+            raise ValueError("max_files must be >= 1")
+
+        def per_file(v, name):
+            if isinstance(v, (list, tuple)):
+                if len(v) != n:
+                    raise ValueError(f"{name}: one value per file expected ({n}), got {len(v)}")
+                return list(v)
+            return [v] * n
+
+        languages, prompts0 = per_file(language, "language"), per_file(initial_prompt, "initial_prompt")
+        hot, prefixes = per_file(hotwords, "hotwords"), per_file(prefix, "prefix")
+        if self.throughput:
+            if any(p is not None for p in prompts0) or clip_timestamps not in ("0", [0], [0.0]) or \
+                    any(p is not None for p in prefixes):
+                raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
+            if len(set(hot)) > 1:
+                raise NotImplementedError("per-file hotwords in throughput mode")
+            return self._pipeline().transcribe_many(
+                audios, language=language, task=task, beam_size=beam_size, best_of=best_of,
+                patience=patience, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
+                no_repeat_ngram_size=no_repeat_ngram_size, hotwords=hot[0] if n else None, temperature=temperature,
+                compression_ratio_threshold=compression_ratio_threshold, log_prob_threshold=log_prob_threshold,
+                no_speech_threshold=no_speech_threshold, suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
+                without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
+                word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
+                append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
+                max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
+                language_detection_segments=language_detection_segments)
+
+        files: dict = {}
+        results: List[List[Segment]] = [[] for _ in range(n)]
+
+        def open_file(f: int) -> SeekState:
+            # per file, as `transcribe`: load, VAD, log-mel, language detection (with language=None), options
+            features, tokenizer, options, info, chunks = self._prepare_file(
+                audios[f], language=languages[f], task=task, beam_size=beam_size, best_of=best_of, patience=patience,
+                length_penalty=length_penalty, repetition_penalty=repetition_penalty,
+                no_repeat_ngram_size=no_repeat_ngram_size, temperature=temperature,
+                compression_ratio_threshold=compression_ratio_threshold, log_prob_threshold=log_prob_threshold,
+                no_speech_threshold=no_speech_threshold, condition_on_previous_text=condition_on_previous_text,
+                prompt_reset_on_temperature=prompt_reset_on_temperature, initial_prompt=prompts0[f],
+                prefix=prefixes[f], suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
+                without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
+                word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
+                append_punctuations=append_punctuations, multilingual=multilingual, vad_filter=vad_filter,
+                vad_parameters=vad_parameters, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
+                hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hot[f],
+                language_detection_threshold=language_detection_threshold,
+                language_detection_segments=language_detection_segments)
+            files[f] = [features, info, chunks]
+            return SeekState(features.shape[1] - 1, tokenizer, options, self.max_length, self.frames_per_second)
+
+        reserved = [0]
+
+        def decode_round(batch):
+            nb = len(batch)
+            opt0 = batch[0][1].options              # everything but the per-file prompt parts is common to the files
+            temps = opt0.temperatures
+            t0 = temps[0] if temps else 0.0
+            sampling = t0 > 0
+            per = (opt0.best_of if sampling else opt0.beam_size)
+            mit = int(round(opt0.max_initial_timestamp / self.time_precision))
+            sot = self.dims.specials.sot
+            with self._lock:                        # one lock scope per round: the slots hold this round's windows
+                self._use_cross_form(opt0.beam_size)      # (a no-op unless another caller changed the form)
+                if nb != reserved[0]:
+                    self.engine.reserve(nb, max(nb * max(per, 1), 8))
+                    reserved[0] = nb
+                # ONE encoder call over the round's windows, into slots 0..nb-1: window i's frames are copied to columns
+                # [i * 3000, i * 3000 + size) of one matrix (the encoder zero-pads each window to 3000 frames itself)
+                mel = torch.zeros((self.dims.n_mels, nb * N_FRAMES), device=files[batch[0][0]][0].device,
+                                  dtype=torch.float32)
+                for i, (f, _, req) in enumerate(batch):
+                    mel[:, i * N_FRAMES: i * N_FRAMES + req.size] = files[f][0][:, req.seek: req.seek + req.size]
+                enc = self.engine.encode(mel, [i * N_FRAMES for i in range(nb)], [req.size for _, _, req in batch])
+                self.engine.cross_kv(enc, 0)
+
+                def first_pass(idx):
+                    if sampling:
+                        # a sampled pass draws noise keyed on (seed, hypothesis index): a file's draws would depend on
+                        # its place in the round, so each window decodes alone, with generate_with_fallback's call
+                        return [self._generate(batch[i][2].prompt, batch[i][1].options, t0, batch[i][2].max_length,
+                                               batch[i][2].window, slot=i) for i in idx]
+                    out: List[Optional[_GenOut]] = [None] * len(idx)
+                    groups: dict = {}
+                    for i in idx:                   # the suppress list is one per generate call
+                        groups.setdefault(tuple(batch[i][1].options.suppress_tokens), []).append(i)
+                    for sup, members in groups.items():
+                        prompts = [batch[i][2].prompt for i in members]
+                        res, _ = self.engine.generate(
+                            members, prompts, beam_size=opt0.beam_size, patience=opt0.patience,
+                            length_penalty=opt0.length_penalty, max_length=[batch[i][2].max_length for i in members],
+                            temperature=t0, suppress_tokens=list(sup),
+                            suppress_blank=opt0.suppress_blank, max_initial_timestamp_index=mit,
+                            with_timestamps=not opt0.without_timestamps,
+                            sot_index=[p.index(sot) if sot in p else -1 for p in prompts], check_every=4,
+                            repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size)
+                        for i, r in zip(members, res):
+                            out[i] = _GenOut(r.tokens, r.score, r.no_speech_prob)
+                    return out
+
+                def fallback_generate(i, t, seed):
+                    _, state, req = batch[i]
+                    return self._generate(req.prompt, state.options, t, req.max_length, seed, slot=i)
+
+                def align(i, current, size, last):
+                    _, state, _ = batch[i]
+                    o = state.options
+                    return self.add_word_timestamps([current], state.tokenizer, size, o.prepend_punctuations,
+                                                    o.append_punctuations, last, slots=[i])
+
+                decode_round_with(batch, first_pass, fallback_generate, align if opt0.word_timestamps else None,
+                                  lambda f, out: results[f].extend(self._segment(d) for d in out))
+
+        def close_file(f: int) -> None:
+            files[f][0] = None                      # the file's log-mel leaves the device with its last window
+
+        run_lockstep(n, max_files, open_file, decode_round, close_file)
+        out = []
+        for f in range(n):
+            _, info, chunks = files[f]
+            segments = results[f]
+            if chunks:
+                from .vad import restore_speech_timestamps
+                segments = list(restore_speech_timestamps(iter(segments), chunks, SAMPLE_RATE))
+            out.append((segments, info))
+        return out
 
     # ------------------------------------------------------------------ word timestamps
     def find_alignment(self, tokenizer: Tokenizer, text_tokens: List[List[int]], num_frames: Union[int, Sequence[int]],
@@ -607,11 +731,6 @@ class WhisperModel:
                     last_speech_timestamp = sub["end"]
                 segments[si][ssi]["words"] = words
         return last_speech_timestamp
-
-
-def _get_end(segments: List[dict]) -> Optional[float]:
-    return next((w["end"] for s in reversed(segments) for w in reversed(s.get("words") or [])),
-                segments[-1]["end"] if segments else None)
 
 
 def _word_means(probs: np.ndarray, wb: np.ndarray) -> List[float]:
