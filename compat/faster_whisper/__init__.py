@@ -15,7 +15,7 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
-from vlog_amd.audio import load_audio as _load_audio  # noqa: E402
+from vlog_amd.audio import load_audio as _load_audio, read_wav as _read_wav, resample_host as _resample_host  # noqa: E402
 from vlog_amd.dims import known_models  # noqa: E402
 from vlog_amd.transcribe import (  # noqa: E402,F401
     BatchedInferencePipeline,
@@ -31,9 +31,16 @@ __version__ = "1.1.1+vlog_amd"
 
 
 def decode_audio(input_file, sampling_rate: int = 16000, split_stereo: bool = False):
-    if split_stereo:
-        raise NotImplementedError("split_stereo is not supported")
-    return _load_audio(input_file, sampling_rate)
+    """faster_whisper.decode_audio for RIFF/WAVE PCM of any supported rate: float32 mono at 16 kHz, or with
+    split_stereo the (left, right) channels of a two-channel file (the host path, vlog_amd.audio.resample_host)."""
+    if not split_stereo:
+        return _load_audio(input_file, sampling_rate)
+    if sampling_rate != 16000:
+        raise ValueError(f"sampling_rate {sampling_rate}: the engine works at 16000 Hz")
+    frames, rate = _read_wav(input_file)
+    if frames.shape[1] != 2:
+        raise ValueError(f"split_stereo needs a two-channel file, got {frames.shape[1]} channel(s)")
+    return tuple(_resample_host(frames, rate, channel=c) for c in (0, 1))
 
 
 def available_models():

@@ -62,6 +62,34 @@ int wm_logmel_finalize(wm_engine* e, float* d_mel, int64_t n_frames, int64_t ld,
  * then runs wm_logmel on the frames whose window lies inside the samples received so far (vlog_amd/ingest.py). */
 int wm_pcm_from_s16(wm_engine* e, const int16_t* d_src, int64_t n, float* d_dst, void* stream);
 
+/* Sample-rate conversion to 16 kHz with downmix: interleaved PCM frames at src_rate -> f32 mono, so a producer
+ * (ffmpeg) can hand over native-rate, native-channel PCM.  The filter is scipy.signal.resample_poly's default:
+ *   g = gcd(16000, rate), up = 16000/g, down = rate/g, m = max(up, down), half = 10 m, N = 2 half + 1 taps
+ *   h[k] = (1/m) sinc((k - half)/m) I0(5 sqrt(1 - ((k - half)/half)^2)) / I0(5),  sinc(x) = sin(pi x)/(pi x)
+ *   h /= sum(h);  h *= up                  (= scipy.signal.firwin(N, 1/m, window=("kaiser", 5.0)) * up)
+ *   mono[i] = mean of the channels of frame i (s16: the exact integer sum times the f32 constant 1/(32768 ch);
+ *             f32: the sum in channel order times 1/ch), or one chosen channel; frames outside the file are zero
+ *   y[j] = sum_i mono[i] h[j down - i up + half]   over 0 <= i < n_total, tap index in [0, 2 half]
+ *   n_out = ceil(n_total up / down); not clipped.  src_rate 16000: up = down = 1, half = 0, the single tap 1.
+ * The taps are evaluated in f64, rounded to f32 and cached on the device per ratio; the sum is f32 in a fixed
+ * order, so output j is the same bits whatever the call's output range or source span.  Supported: N <= 16384
+ * (max(up, down) <= 819: 8000, 11025, 12000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400, 192000 Hz
+ * among others), 1 .. 8 channels.
+ *
+ * wm_resample_plan: pure host, no GPU touched: 0, or -1 for an unsupported rate (the message names the rate).
+ * wm_resample_taps: the f32 taps the kernel uses, h_taps[2*half_len+1]; pure host.
+ * wm_resample: outputs [out0, out0+n_out) of the whole-file resampling into d_dst[0..n_out).  d_src holds source
+ * frames [src_offset, src_offset+n_src) (interleaved, fmt 0 = s16, 1 = f32).  channel -1 = mean of all, else that
+ * channel.  n_total = frames in the file, or -1 "end not yet known" (streaming).  Output j reads frames
+ * ceil((j down - half)/up) .. floor((j down + half)/up), clipped to the file.  Fails (-1, nothing launched) on an
+ * unsupported rate, bad channels / channel, a negative length, src_offset + n_src > n_total, out0 + n_out >
+ * ceil(n_total up / down), or a needed frame inside the file that the span does not hold (with n_total = -1: any
+ * frame at or past src_offset + n_src).  n_out == 0 succeeds and launches nothing. */
+int wm_resample_plan(int32_t src_rate, int32_t* up, int32_t* down, int32_t* half_len);
+int wm_resample_taps(int32_t src_rate, float* h_taps);
+int wm_resample(wm_engine* e, const void* d_src, int32_t fmt, int32_t channels, int32_t channel, int32_t src_rate,
+                int64_t src_offset, int64_t n_src, int64_t n_total, int64_t out0, int64_t n_out, float* d_dst, void* stream);
+
 /* Per-frame log energy (dB) of ceil(n_samples / frame) frames, the speech-probability input of the VAD
  * stand-in (faster-whisper's Silero VAD [FW↑], reached via vad_filter=True at worker/transcription.py:110). */
 int wm_frame_energy(wm_engine* e, const float* d_pcm, int64_t n_samples, int32_t frame, float* d_db, void* stream);

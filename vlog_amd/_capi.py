@@ -19,6 +19,7 @@ SYMBOLS = (
     "wm_logmel", "wm_logmel_finalize", "wm_encode", "wm_reserve", "wm_cross_kv", "wm_generate", "wm_forward",
     "wm_detect_language", "wm_frame_energy", "wm_pcm_from_s16", "wm_vad_probs", "wm_cross_fp8_quantize", "wm_align", "wm_align_batch", "wm_dtw", "wm_device_bytes", "wm_profile_classes", "wm_profile_name", "wm_profile", "wm_profile_select",
     "wm_profile_read", "wm_set_option", "wm_get_option", "wm_encoder_attention",
+    "wm_resample_plan", "wm_resample_taps", "wm_resample",
 )
 
 
@@ -82,6 +83,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "wm_detect_language": (C.c_int, [vp, i32, C.POINTER(i32), i32, i32, C.POINTER(C.c_float), vp]),
         "wm_vad_probs": (C.c_int, [vp, vp, vp, i64, vp, vp, vp]),
         "wm_pcm_from_s16": (C.c_int, [vp, vp, i64, vp, vp]),
+        "wm_resample_plan": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "wm_resample_taps": (C.c_int, [i32, C.POINTER(C.c_float)]),
+        "wm_resample": (C.c_int, [vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i64, vp, vp]),
         "wm_cross_fp8_quantize": (C.c_int, [vp, vp, i64, vp, vp, vp]),
         "wm_align": (C.c_int, [vp, i32, i32, C.POINTER(i32), i32, C.POINTER(i32), i32, C.POINTER(i32), i32, i32,
                                C.POINTER(C.c_float), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]),

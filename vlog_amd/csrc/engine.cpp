@@ -32,6 +32,8 @@ void launch_logmel_clamp(float*, long long, long long, long long, const unsigned
 void launch_ordered_to_float(const unsigned int*, float*, hipStream_t);
 void launch_frame_energy(const float*, long long, int, int, float*, hipStream_t);
 void launch_pcm_s16(const short*, long long, float*, hipStream_t);
+void launch_resample(const void*, int, int, int, long long, long long, long long, const float*, int, int, int, int,
+                     long long, long long, float*, hipStream_t);
 void launch_layernorm(const float*, long long, const int*, int, int, const float*, const float*, bf16*, long long, hipStream_t);
 void launch_embed(const int*, const int*, const bf16*, const float*, float*, int, int, int, int, hipStream_t, int*);
 void launch_im2col_conv1(const float*, long long, const int*, const int*, int, int, int, bf16*, hipStream_t);
@@ -263,6 +265,12 @@ struct wm_engine {
   int tf_nwin = 0;
   DevBuf a_logits, a_attn, a_next, a_probs, a_rowsum, a_z, a_mat, a_cost, a_trace, a_pi, a_pj, a_plen, a_meta;
   DevBuf prof_dbytes;        // device counters (attention kernels add the bytes they actually read)
+  // wm_resample: per ratio (up, down), the f32 taps in polyphase order [up][T] on the device (built once)
+  struct RsTaps {
+    int T = 0;
+    DevBuf pp;
+  };
+  std::map<std::pair<int, int>, RsTaps> rs_taps;
   hipEvent_t ev_get() {
     if (ev_pool.empty()) {
       hipEvent_t ev;
@@ -2500,6 +2508,81 @@ int* dec_proj_option(wm_engine* e, const std::string& k, const char* who, bool* 
   throw std::runtime_error(std::string(who) + ": unknown projection " + pj);
 }
 
+// ---- sample-rate conversion to 16 kHz (wm_resample*): the plan and the f64 taps of the definition in
+// include/whisper_mi355.h (scipy.signal.resample_poly's default filter), pure host
+struct RsPlan {
+  int up, down, half;
+};
+constexpr int kRsMaxTaps = 16384;
+
+RsPlan rs_plan(int32_t rate, const char* who) {
+  if (rate <= 0) throw std::runtime_error(std::string(who) + ": unsupported sample rate " + std::to_string(rate) + " Hz");
+  int a = 16000, b = rate;
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  RsPlan p{16000 / a, rate / a, 0};
+  if (p.up == 1 && p.down == 1) return p;              // the identity: one tap of 1, downmix only
+  const long long m = std::max(p.up, p.down);
+  if (20 * m + 1 > kRsMaxTaps)
+    throw std::runtime_error(std::string(who) + ": unsupported sample rate " + std::to_string(rate) + " Hz: 16000/" +
+                             std::to_string(rate) + " = " + std::to_string(p.up) + "/" + std::to_string(p.down) +
+                             " needs " + std::to_string(20 * m + 1) + " filter taps (at most " +
+                             std::to_string(kRsMaxTaps) + ")");
+  p.half = (int)(10 * m);
+  return p;
+}
+
+// I0 on [0, 5] by its power series sum_k ((x/2)^2)^k / (k!)^2 (terms fall below 1e-18 of the sum within 30)
+double bessel_i0(double x) {
+  const double q = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 64 && term > 1e-18 * sum; ++k) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+  }
+  return sum;
+}
+
+std::vector<double> rs_taps_f64(const RsPlan& p) {
+  if (p.half == 0) return {1.0};
+  const int m = std::max(p.up, p.down), n = 2 * p.half + 1;
+  const double pi = 3.14159265358979323846, i0b = bessel_i0(5.0);
+  std::vector<double> h(n);
+  double sum = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double u = (double)(k - p.half), x = u / m, r = u / p.half;
+    const double s = u == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
+    h[k] = s / m * (bessel_i0(5.0 * std::sqrt(1.0 - r * r)) / i0b);
+    sum += h[k];
+  }
+  for (double& v : h) v = v / sum * p.up;
+  return h;
+}
+
+// The ratio's f32 taps on the device in polyphase order, pp[q * T + t] = h[q + t up] (zero where q + t up > 2 half;
+// the kernel reads none of those)
+const float* rs_device_taps(wm_engine* e, const RsPlan& p, int* T) {
+  auto& c = e->rs_taps[{p.up, p.down}];
+  if (!c.pp.p) {
+    const std::vector<double> h = rs_taps_f64(p);
+    // row stride: the taps per phase, made odd so that the lanes of a wave (each on its own phase q) spread over
+    // the LDS banks (44.1 kHz: 56 taps per phase put every lane on one of four banks)
+    const int n = (int)h.size(), t = ((n + p.up - 1) / p.up) | 1;
+    std::vector<float> pp((size_t)p.up * t, 0.f);
+    for (int k = 0; k < n; ++k) pp[(size_t)(k % p.up) * t + k / p.up] = (float)h[k];
+    c.pp.ensure(pp.size() * sizeof(float));
+    HIP_OK(hipMemcpy(c.pp.p, pp.data(), pp.size() * sizeof(float), hipMemcpyHostToDevice));
+    c.T = t;
+  }
+  *T = c.T;
+  return c.pp.as<float>();
+}
+
+inline long long ceil_div(long long a, long long b) { return a >= 0 ? (a + b - 1) / b : -((-a) / b); }   // b > 0
+
 }  // namespace
 
 extern "C" {
@@ -2576,6 +2659,7 @@ void wm_destroy(wm_engine* e) {
                     &e->d_win_slot, &e->d_hyp_out, &e->d_res_tok, &e->d_res_len, &e->d_res_cum, &e->d_res_ns, &e->d_res_lp,
                     &e->d_res_lp_o, &e->d_ev, &e->d_hyp_begin, &e->d_hyp_maxlen, &e->d_win_len, &e->d_win_maxlen})
     b->release();
+  for (auto& kv : e->rs_taps) kv.second.pp.release();
   if (e->st2) (void)hipStreamDestroy(e->st2);
   if (e->gst) (void)hipStreamDestroy(e->gst);
   if (e->ev_g0) (void)hipEventDestroy(e->ev_g0);
@@ -2749,6 +2833,66 @@ int wm_pcm_from_s16(wm_engine* e, const int16_t* d_src, int64_t n, float* d_dst,
   return guarded(e, [&] {
     if (n < 0) throw std::runtime_error("wm_pcm_from_s16: negative length");
     launch_pcm_s16((const short*)d_src, n, d_dst, (hipStream_t)stream);
+  });
+}
+
+int wm_resample_plan(int32_t src_rate, int32_t* up, int32_t* down, int32_t* half_len) {
+  try {
+    const RsPlan p = rs_plan(src_rate, "wm_resample_plan");
+    if (up) *up = p.up;
+    if (down) *down = p.down;
+    if (half_len) *half_len = p.half;
+    return 0;
+  } catch (const std::exception& ex) {
+    g_err = ex.what();
+    return -1;
+  }
+}
+
+int wm_resample_taps(int32_t src_rate, float* h_taps) {
+  try {
+    if (!h_taps) throw std::runtime_error("wm_resample_taps: null argument");
+    const std::vector<double> h = rs_taps_f64(rs_plan(src_rate, "wm_resample_taps"));
+    for (size_t k = 0; k < h.size(); ++k) h_taps[k] = (float)h[k];
+    return 0;
+  } catch (const std::exception& ex) {
+    g_err = ex.what();
+    return -1;
+  }
+}
+
+int wm_resample(wm_engine* e, const void* d_src, int32_t fmt, int32_t channels, int32_t channel, int32_t src_rate,
+                int64_t src_offset, int64_t n_src, int64_t n_total, int64_t out0, int64_t n_out, float* d_dst,
+                void* stream) {
+  return guarded(e, [&] {
+    const RsPlan p = rs_plan(src_rate, "wm_resample");
+    auto S = [](long long v) { return std::to_string(v); };
+    if (fmt != 0 && fmt != 1) throw std::runtime_error("wm_resample: fmt " + S(fmt) + " (0 = s16, 1 = f32)");
+    if (channels < 1 || channels > 8) throw std::runtime_error("wm_resample: channels " + S(channels) + " (1 .. 8)");
+    if (channel < -1 || channel >= channels)
+      throw std::runtime_error("wm_resample: channel " + S(channel) + " of " + S(channels) + " (-1 = mean of all)");
+    if (src_offset < 0 || n_src < 0 || out0 < 0 || n_out < 0 || n_total < -1)
+      throw std::runtime_error("wm_resample: negative offset or length");
+    if (n_total >= 0 && src_offset + n_src > n_total)
+      throw std::runtime_error("wm_resample: source span [" + S(src_offset) + ", " + S(src_offset + n_src) +
+                               ") past the end of the file (" + S(n_total) + " frames)");
+    if (n_total >= 0 && out0 + n_out > ceil_div(n_total * p.up, p.down))
+      throw std::runtime_error("wm_resample: outputs [" + S(out0) + ", " + S(out0 + n_out) + ") past the end of the output (" +
+                               S(ceil_div(n_total * p.up, p.down)) + " samples)");
+    if (n_out == 0) return;
+    if (!d_dst || (!d_src && n_src > 0)) throw std::runtime_error("wm_resample: null buffer");
+    // frames the outputs read, clipped to the file: all of them must be in the span given
+    const long long lo = std::max(0LL, ceil_div(out0 * p.down - p.half, p.up));
+    long long hi = ((out0 + n_out - 1) * p.down + p.half) / p.up;
+    if (n_total >= 0) hi = std::min<long long>(hi, n_total - 1);
+    if (hi >= lo && (lo < src_offset || hi >= src_offset + n_src))
+      throw std::runtime_error("wm_resample: outputs [" + S(out0) + ", " + S(out0 + n_out) + ") need source frames [" +
+                               S(lo) + ", " + S(hi) + "], missing from the span given [" + S(src_offset) + ", " +
+                               S(src_offset + n_src) + ")");
+    int T = 0;
+    const float* pp = rs_device_taps(e, p, &T);
+    launch_resample(d_src, fmt, channels, channel, src_offset, n_src, n_total, pp, p.up, p.down, p.half, T, out0, n_out,
+                    d_dst, (hipStream_t)stream);
   });
 }
 

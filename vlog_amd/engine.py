@@ -261,6 +261,47 @@ class GpuEngine:
                                                  self.stream_ptr()), "wm_frame_energy")
         return out.cpu().numpy()[: (n + frame - 1) // frame]
 
+    # ------------------------------------------------------------------ sample-rate conversion
+    def resample_plan(self, rate: int) -> Tuple[int, int, int]:
+        """wm_resample_plan: (up, down, half) of rate -> 16 kHz; RuntimeError for a rate the kernel does not support."""
+        up, down, half = C.c_int32(), C.c_int32(), C.c_int32()
+        _capi.check(self.lib.wm_resample_plan(int(rate), C.byref(up), C.byref(down), C.byref(half)), "wm_resample_plan")
+        return up.value, down.value, half.value
+
+    def resample_into(self, src: torch.Tensor, channels: int, rate: int, src_offset: int, n_total: int, out0: int,
+                      n_out: int, dst: torch.Tensor, channel: int = -1) -> None:
+        """wm_resample: outputs [out0, out0 + n_out) of the file into dst[:n_out]; `src` (contiguous device int16 or
+        float32) holds frames [src_offset, src_offset + src.numel() // channels); n_total -1: end not yet known."""
+        if src.dtype not in (torch.int16, torch.float32) or not src.is_contiguous() or src.device != self.device:
+            raise ValueError("resample: contiguous int16 or float32 frames on the engine's device")
+        if dst.dtype != torch.float32 or not dst.is_contiguous() or dst.numel() < n_out or dst.device != self.device:
+            raise ValueError("resample: dst must be a contiguous float32 device tensor of >= n_out samples")
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.wm_resample(self.h, C.c_void_p(src.data_ptr()), 0 if src.dtype == torch.int16 else 1,
+                                             channels, channel, int(rate), src_offset, src.numel() // max(channels, 1),
+                                             n_total, out0, n_out, C.c_void_p(dst.data_ptr()), self.stream_ptr()),
+                        "wm_resample")
+
+    def resample(self, frames, rate: int, channel: int = -1) -> torch.Tensor:
+        """PCM frames [n] or [n, ch] (numpy or tensor, int16 or float32) at `rate` Hz -> f32 mono at 16 kHz on the
+        device, [ceil(n up / down)]: the mean of the channels (or channel `channel`) through the polyphase filter of
+        vlog_amd/audio.py (resample_host is the same definition in f64)."""
+        if isinstance(frames, np.ndarray):
+            frames = np.ascontiguousarray(frames)
+            frames = torch.from_numpy(frames if frames.flags.writeable else frames.copy())
+        x = frames
+        if x.dim() == 1:
+            x = x[:, None]
+        if x.dim() != 2 or x.dtype not in (torch.int16, torch.float32):
+            raise ValueError("resample: frames must be int16 or float32, [n] or [n, channels]")
+        n, ch = x.shape
+        x = x.to(self.device).contiguous()
+        up, down, _ = self.resample_plan(rate)
+        n_out = -((-n * up) // down)
+        out = torch.empty(n_out, dtype=torch.float32, device=self.device)
+        self.resample_into(x, ch, rate, 0, n, 0, n_out, out, channel)
+        return out
+
     def features(self, pcm: torch.Tensor) -> torch.Tensor:
         """faster-whisper FeatureExtractor(audio): clamped log-mel [n_mels, N//160 + 1] on device."""
         mel, gmax = self.logmel(pcm)

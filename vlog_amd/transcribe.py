@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import segments as segs
-from .audio import load_audio
+from .audio import mono_f32, read_wav
 from .seek_state import SeekState, decode_round_with, fallback_ladder, run_lockstep, window_max_length
 from .dims import CHUNK_LENGTH, HOP_LENGTH, N_FRAMES, SAMPLE_RATE, TIME_PRECISION
 from .tokenizer import Tokenizer
@@ -223,6 +223,16 @@ class WhisperModel:
         return Tokenizer(self.dims, task=task, language=language, tokenizer_json=self._tokenizer_json, seed=self._tok_seed)
 
     # ------------------------------------------------------------------ features / encoder
+    def _load_audio(self, src) -> np.ndarray:
+        """A WAV path / file object -> float32 mono at 16 kHz.  A 16 kHz file is int16 / 32768 with the channels
+        averaged (audio.load_audio's path, bit for bit); any other rate is downmixed and resampled on the device
+        (Engine.resample) and copied back for the host stages (VAD, chunk collection)."""
+        frames, rate = read_wav(src)
+        if rate == SAMPLE_RATE:
+            return mono_f32(frames)
+        with self._lock:
+            return self.engine.resample(frames, rate).cpu().numpy()
+
     def _features(self, audio: np.ndarray) -> torch.Tensor:
         return self.engine.features(torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)))
 
@@ -351,7 +361,7 @@ class WhisperModel:
         """What `transcribe` does for one file before its seek loop: load, VAD, log-mel, language, tokenizer, options.
         -> (features, tokenizer, options, info, speech_chunks)"""
         if not isinstance(audio, np.ndarray):
-            audio = load_audio(audio)
+            audio = self._load_audio(audio)
         audio = np.asarray(audio, dtype=np.float32)
         duration = audio.shape[0] / SAMPLE_RATE
         duration_after_vad = duration
@@ -1040,7 +1050,7 @@ class BatchedInferencePipeline:
             audio = audio.pcm
         else:
             if not isinstance(audio, np.ndarray):
-                audio = load_audio(audio)
+                audio = m._load_audio(audio)
             audio = np.asarray(audio, dtype=np.float32)
             duration = audio.shape[0] / SAMPLE_RATE
             with m._lock:
