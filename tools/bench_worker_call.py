@@ -18,6 +18,11 @@ usage: python tools/bench_worker_call.py [--minutes-seq 5] [--minutes-tp 60] [--
 worker's call per file): for each N, N distinct clips of --minutes-seq minutes with N files in flight; one JSON line per
 point with the RTFx summed over the files and the milliseconds per decoder pass of the shared first-pass decodes (wall
 time inside engine.generate over its pass count); N = 1 is `transcribe` on one file.
+
+--sections 1,2,4,8,16 [--sections-in-flight K]: the worker's call on ONE clip of --minutes-seq minutes with
+transcribe(sections=N) (the file's sections decoded in lockstep); one JSON line per N with the sections the plan gave,
+the wall times of --repeats calls (from the call to the VTT string), the RTFx of their median, and the decoder-pass
+figures of --files.  N = 0 calls transcribe without the argument, so the same file measures a tree from before it.
 """
 import argparse
 import json
@@ -51,16 +56,8 @@ def worker_call(model, wav, temperature=None):
     return time.perf_counter() - t, " ".join(parts), info, len(segs), len(vtt)
 
 
-def many_files(model, args, spec, tmp):
-    counts = [int(v) for v in args.files.split(",")]
-    n_win = int(round(args.minutes_seq * 2))
-    paths = []
-    for f in range(max(counts)):
-        path = os.path.join(tmp, f"file{f}.wav")
-        write_wav(path, np.concatenate([speech_like(30.0, 100 * f + i) for i in range(n_win)]))
-        paths.append(path)
-    audio_s = n_win * 30.0
-    eng = model.engine
+def time_generate(eng):
+    """Wraps eng.generate -> the dict that accumulates its wall seconds, decoder passes, row steps and calls."""
     acc = {"s": 0.0, "passes": 0, "rows": 0, "calls": 0}
     inner = eng.generate
 
@@ -76,6 +73,62 @@ def many_files(model, args, spec, tmp):
         return r
 
     eng.generate = timed_generate
+    return acc
+
+
+def sectioned(model, args, spec, tmp):
+    counts = [int(v) for v in args.sections.split(",")]
+    n_win = int(round(args.minutes_seq * 2))
+    path = os.path.join(tmp, "long.wav")
+    write_wav(path, np.concatenate([speech_like(30.0, i) for i in range(n_win)]))
+    audio_s = n_win * 30.0
+    acc = time_generate(model.engine)
+
+    def call(n):
+        kw = dict(language=None, task="transcribe", beam_size=5, vad_filter=True)
+        if args.temperature is not None:
+            kw["temperature"] = args.temperature
+        if n > 0:
+            kw["sections"] = n
+            if args.sections_in_flight is not None:
+                kw["sections_in_flight"] = args.sections_in_flight
+        t = time.perf_counter()
+        segments, info = model.transcribe(path, **kw)
+        segs = [{"start": s.start, "end": s.end, "text": s.text} for s in segments]
+        generate_webvtt(segs)
+        return time.perf_counter() - t, info, len(segs)
+
+    call(0)                                                        # warm-up (allocations, kernels)
+    for n in counts:
+        call(n)                                                    # (the slots and rows of this point)
+        acc.update(s=0.0, passes=0, rows=0, calls=0)
+        walls = []
+        for _ in range(args.repeats):
+            dt, info, nseg = call(n)
+            walls.append(dt)
+        bounds = getattr(info.transcription_options, "section_frames", None)
+        med = float(np.median(walls))
+        print(json.dumps({"model": args.model, "weights": spec, "sections": n if n > 0 else None,
+                          "sections_planned": len(bounds) if bounds else 1,
+                          "sections_in_flight": args.sections_in_flight, "audio_s": audio_s,
+                          "duration_after_vad": round(info.duration_after_vad, 2),
+                          "wall_s": [round(w, 3) for w in walls], "rtfx": round(audio_s / med, 2),
+                          "rtfx_runs": [round(audio_s / w, 2) for w in walls], "segments": nseg,
+                          "generate_calls": acc["calls"] // args.repeats, "decoder_passes": acc["passes"] // args.repeats,
+                          "ms_per_decoder_pass": round(1e3 * acc["s"] / max(acc["passes"], 1), 4),
+                          "rows_per_pass": round(acc["rows"] / max(acc["passes"], 1), 2)}), flush=True)
+
+
+def many_files(model, args, spec, tmp):
+    counts = [int(v) for v in args.files.split(",")]
+    n_win = int(round(args.minutes_seq * 2))
+    paths = []
+    for f in range(max(counts)):
+        path = os.path.join(tmp, f"file{f}.wav")
+        write_wav(path, np.concatenate([speech_like(30.0, 100 * f + i) for i in range(n_win)]))
+        paths.append(path)
+    audio_s = n_win * 30.0
+    acc = time_generate(model.engine)
     kw = dict(language=None, task="transcribe", beam_size=5, vad_filter=True)
     if args.temperature is not None:
         kw["temperature"] = args.temperature
@@ -109,6 +162,12 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="decode steps launched eagerly (decode_graph=0)")
     ap.add_argument("--files", default=None,
                     help="comma-separated numbers of files in flight: measure transcribe_many instead (module docstring)")
+    ap.add_argument("--sections", default=None,
+                    help="comma-separated section counts: measure transcribe(sections=N) on one clip (module docstring); "
+                         "0 = the call without the argument")
+    ap.add_argument("--sections-in-flight", type=int, default=None,
+                    help="sections decoded per round (default: all; 1 = one after another, the A/B baseline)")
+    ap.add_argument("--repeats", type=int, default=3, help="timed calls per --sections point")
     args = ap.parse_args()
     spec = f"synthetic:{args.model}:0" + ("" if args.random_weights else ":margin")
     model = WhisperModel(spec, device="cpu", compute_type="int8", eot_after=110)
@@ -117,6 +176,8 @@ def main():
     tmp = tempfile.mkdtemp()
     if args.files:
         return many_files(model, args, spec, tmp)
+    if args.sections:
+        return sectioned(model, args, spec, tmp)
 
     def clip(minutes, name):
         n = int(round(minutes * 2))

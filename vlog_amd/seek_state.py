@@ -8,6 +8,9 @@ so that one driver can hold several files and decode the next window of each in 
   SeekState.next_request() -> the next window to decode (seek, size, prompt, seed base), or None at the file's end
   SeekState.consume(...)   -> takes the window's decode result, returns the segments to yield
 
+The same scheduler decodes the sections of ONE file (`WhisperModel.transcribe(sections=N)`): plan_sections cuts the
+file at long silences, and each section is a SeekState confined to its frame range (clip_frames).
+
 Nothing here touches the GPU (no torch import): the decode, the fallback passes and the alignment are callables the
 driver supplies, so tests run both the state and the scheduler against a scripted backend.
 """
@@ -82,21 +85,28 @@ class SeekState:
     """One file's position in the sequential mode: seek, clips, previous text, window counter, segment id."""
 
     def __init__(self, content_frames: int, tokenizer, options, model_max_length: int = 448,
-                 frames_per_second: int = FRAMES_PER_SECOND):
+                 frames_per_second: int = FRAMES_PER_SECOND, clip_frames: Optional[Tuple[int, int]] = None):
+        """clip_frames: one exact (start, end) frame range that replaces the clip list of options.clip_timestamps (a
+        section of plan_sections).  The state is then a file of its own between those frames: `prefix` applies only
+        where seek == 0 (so to the section that starts the file), `initial_prompt` seeds this section's history as it
+        seeds a file's, and the window counter (so the fallback seeds window + i) starts at 0."""
         self.content_frames = content_frames
         self.tokenizer = tokenizer
         self.options = options
         self.model_max_length = model_max_length
         self.frames_per_second = frames_per_second
-        ct = options.clip_timestamps
-        if isinstance(ct, str):
-            ct = [float(t) for t in (ct.split(",") if ct else [])]
-        seek_points = [round(t * frames_per_second) for t in ct]
-        if not seek_points:
-            seek_points.append(0)
-        if len(seek_points) % 2 == 1:
-            seek_points.append(content_frames)
-        self.seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
+        if clip_frames is not None:
+            self.seek_clips = [(int(clip_frames[0]), int(clip_frames[1]))]
+        else:
+            ct = options.clip_timestamps
+            if isinstance(ct, str):
+                ct = [float(t) for t in (ct.split(",") if ct else [])]
+            seek_points = [round(t * frames_per_second) for t in ct]
+            if not seek_points:
+                seek_points.append(0)
+            if len(seek_points) % 2 == 1:
+                seek_points.append(content_frames)
+            self.seek_clips = list(zip(seek_points[::2], seek_points[1::2]))
         self.idx = 0                    # id of the last segment yielded
         self.clip_idx = 0
         self.seek = self.seek_clips[0][0]
@@ -188,9 +198,18 @@ def run_lockstep(n_files: int, max_files: int, open_file: Callable[[int], SeekSt
     driver drops what it held for it).  -> the number of rounds."""
     if max_files < 1:
         raise ValueError("max_files must be >= 1")
+    return sum(1 for _ in iter_lockstep(n_files, max_files, open_file, decode_round, close_file))
+
+
+def iter_lockstep(n_files: int, max_files: int, open_file: Callable[[int], SeekState],
+                  decode_round: Callable[[List[Tuple[int, SeekState, WindowRequest]]], None],
+                  close_file: Optional[Callable[[int], None]] = None):
+    """run_lockstep as a generator: yields the round's batch after every decode_round, so a driver that streams its
+    output (the sections of one file) can hand on what the round made final before the next round starts."""
+    if max_files < 1:
+        raise ValueError("max_files must be >= 1")
     pending = deque(range(n_files))
     active: List[Tuple[int, SeekState]] = []
-    rounds = 0
     while pending or active:
         batch: List[Tuple[int, SeekState, WindowRequest]] = []
         keep: List[Tuple[int, SeekState]] = []
@@ -217,8 +236,7 @@ def run_lockstep(n_files: int, max_files: int, open_file: Callable[[int], SeekSt
         for _, state, _ in batch:
             if state._request is not None:
                 raise RuntimeError("run_lockstep: decode_round left a request unconsumed")
-        rounds += 1
-    return rounds
+        yield batch
 
 
 def decode_round_with(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
@@ -236,3 +254,75 @@ def decode_round_with(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
         decode = fallback_ladder(lambda t, seed, i=i: fallback_generate(i, t, seed), state.tokenizer.decode, state.options,
                                  seed=req.window, first=firsts[i])
         emit(f, state.consume(decode, (lambda cur, size, last, i=i: align(i, cur, size, last)) if align else None))
+
+
+# ---------------------------------------------------------------------------------------------------- sections
+# One long file cut at a few long silences into contiguous sections, each decoded by a SeekState of its own
+# (clip_frames) while run_lockstep / iter_lockstep decodes the sections together as it decodes files.  The three
+# thresholds below are design choices, not measurements.
+MAX_SECTIONS = 32
+SECTION_MIN_JOIN_SILENCE_S = 0.5    # a VAD join is a cut candidate only when at least this much silence was removed there
+SECTION_JOIN_REACH = 0.5            # a join may lie this fraction of an even section's length away from its target
+SECTION_ENERGY_REACH_S = 3.0        # without VAD, the quietest 20 ms frame is sought this far to each side of a target
+ENERGY_FRAME_MEL = 2                # a wm_frame_energy frame of 320 samples is two mel frames
+
+
+def chunk_joins(speech_chunks: Sequence[dict], hop_length: int = HOP_LENGTH,
+                sampling_rate: int = SAMPLE_RATE) -> List[Tuple[int, float]]:
+    """[(frame, removed_silence_seconds)] for plan_sections: one entry per boundary between two collected speech
+    chunks (vad.collect_chunks), at the cumulative chunk samples // hop_length of the concatenated audio."""
+    out: List[Tuple[int, float]] = []
+    cum = 0
+    for a, b in zip(speech_chunks[:-1], speech_chunks[1:]):
+        cum += a["end"] - a["start"]
+        out.append((cum // hop_length, (b["start"] - a["end"]) / sampling_rate))
+    return out
+
+
+def plan_sections(content_frames: int, n: int, joins: Optional[Sequence[Tuple[int, float]]] = None,
+                  energy: Optional[Sequence[float]] = None) -> List[Tuple[int, int]]:
+    """Contiguous frame ranges [(start, end)] that cover [0, content_frames), at most n of them, each at least
+    N_FRAMES long; in mel frames of the audio the seek loop sees (after VAD concatenation).  The result depends on the
+    arguments alone.
+
+    Cut j aims at t_j = round(j * content_frames / n).  With `joins` (VAD ran; see chunk_joins) it is the join nearest
+    to t_j among those with >= SECTION_MIN_JOIN_SILENCE_S removed and within SECTION_JOIN_REACH * content_frames / n
+    frames of t_j (ties: the longer silence, then the lower frame); a target without such a join loses its cut, so a
+    speech chunk is never cut.  With `energy` (dB per 20 ms frame, engine.frame_energy_db(audio, 320)) it is the first
+    mel frame of the quietest energy frame within SECTION_ENERGY_REACH_S of t_j (ties: nearest to t_j, then the lower).
+    With neither, the cuts are the targets.  A file too short for n sections of N_FRAMES gets fewer targets, and cuts
+    that would still leave a section shorter than N_FRAMES are dropped, first the one whose shorter neighbouring
+    section is shortest (ties: the lower frame)."""
+    if not 1 <= n <= MAX_SECTIONS:
+        raise ValueError(f"sections must be between 1 and {MAX_SECTIONS}, got {n}")
+    content_frames = max(int(content_frames), 0)
+    n = max(1, min(n, content_frames // N_FRAMES))
+    cuts = set()
+    for j in range(1, n):
+        t = round(j * content_frames / n)
+        if joins is not None:
+            reach = SECTION_JOIN_REACH * content_frames / n
+            cand = [(abs(f - t), -s, f) for f, s in joins
+                    if s >= SECTION_MIN_JOIN_SILENCE_S and abs(f - t) <= reach and 0 < f < content_frames]
+            if cand:
+                cuts.add(min(cand)[2])
+        elif energy is not None:
+            reach = int(SECTION_ENERGY_REACH_S * FRAMES_PER_SECOND)
+            lo = max(0, -((reach - t) // ENERGY_FRAME_MEL))             # ceil((t - reach) / 2)
+            hi = min(len(energy) - 1, (t + reach) // ENERGY_FRAME_MEL)
+            cand = [(float(energy[e]), abs(e * ENERGY_FRAME_MEL - t), e) for e in range(lo, hi + 1)]
+            if cand:
+                f = min(cand)[2] * ENERGY_FRAME_MEL
+                if 0 < f < content_frames:
+                    cuts.add(f)
+        else:
+            cuts.add(t)
+    cuts = sorted(cuts)
+    while cuts:
+        edges = [0] + cuts + [content_frames]
+        lengths = [b - a for a, b in zip(edges[:-1], edges[1:])]
+        if min(lengths) >= N_FRAMES:
+            break
+        cuts.remove(min(cuts, key=lambda c: (min(lengths[cuts.index(c)], lengths[cuts.index(c) + 1]), c)))
+    edges = [0] + cuts + [content_frames]
+    return list(zip(edges[:-1], edges[1:]))

@@ -35,7 +35,8 @@ import torch
 
 from . import segments as segs
 from .audio import mono_f32, read_wav
-from .seek_state import SeekState, decode_round_with, fallback_ladder, run_lockstep, window_max_length
+from .seek_state import (ENERGY_FRAME_MEL, MAX_SECTIONS, SeekState, chunk_joins, decode_round_with, fallback_ladder,
+                         iter_lockstep, plan_sections, run_lockstep, window_max_length)
 from .dims import CHUNK_LENGTH, HOP_LENGTH, N_FRAMES, SAMPLE_RATE, TIME_PRECISION
 from .tokenizer import Tokenizer
 from .weights import resolve_model
@@ -105,6 +106,7 @@ class TranscriptionOptions:
     clip_timestamps: Union[str, List[float]]
     hallucination_silence_threshold: Optional[float]
     hotwords: Optional[str]
+    section_frames: Optional[List[Tuple[int, int]]] = None     # transcribe(sections=N): the (start, end) chosen
 
 
 @dataclass
@@ -303,7 +305,29 @@ class WhisperModel:
                    max_new_tokens: Optional[int] = None, chunk_length: Optional[int] = None,
                    clip_timestamps: Union[str, List[float]] = "0", hallucination_silence_threshold: Optional[float] = None,
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
-                   language_detection_segments: int = 1):
+                   language_detection_segments: int = 1, sections: Optional[int] = None,
+                   sections_in_flight: Optional[int] = None):
+        """faster-whisper's `WhisperModel.transcribe`, plus two arguments of this engine:
+
+        sections: cut the file at up to sections - 1 long silences into contiguous sections (seek_state.plan_sections:
+        near the even split points, at a VAD chunk join with at least 0.5 s removed, or without VAD at the quietest
+        20 ms within 3 s; every section at least 30 s) and decode the sections in lockstep, one ragged engine.generate
+        per round over the next window of every section, as transcribe_many decodes files.  Inside a section the
+        sequential loop is unchanged (previous-text prompt, timestamp seek, fallback ladder, word-timestamp seek).
+        What differs from sections=1: the first window after each cut starts without previous text, as after a prompt
+        reset; `initial_prompt` seeds every section; `prefix` applies to section 0 only; the window counter, and so the
+        fallback seeds, restart at 0 in every section.  Default: the VLOG_AMD_SECTIONS environment variable, else 1
+        (today's one-file loop, untouched).  1..32; not with throughput mode or clip_timestamps.  The bounds chosen are
+        in info.transcription_options.section_frames.
+        sections_in_flight: sections decoded per round (default: all); 1 decodes them one after another, which gives
+        the same transcript and is the baseline of the measurement.
+        Measured on one MI355X (large-v3 margin weights, the worker's call on a 12-minute clip, 591 s after VAD;
+        tools/bench_worker_call.py --sections, profiles/worker_call_sections.jsonl): sections -> RTFx /
+        rows per decoder pass / ms per pass: 1 -> 144 / 5.0 / 2.11, 2 -> 237 / 9.6 / 2.32, 4 -> 345 / 18.3 / 2.90,
+        8 -> 476 / 30.0 / 3.11, 16 (13 after the 30 s rule) -> 551 / 48.3 / 3.50; the same 13 sections one after
+        another (sections_in_flight=1): 103.  The doublings gain x1.65, 1.46, 1.38, 1.16 (every cut adds a short
+        window, and load, VAD and log-mel are not shared), so by the rule of transcribe_many's max_files (the last
+        doubling that gains at least x1.5) the recommended value is 2; the default stays 1."""
         for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
             if val != default:
@@ -312,6 +336,16 @@ class WhisperModel:
             raise NotImplementedError("chunk_length other than 30 s is not supported")
         if task not in ("transcribe", "translate"):
             raise ValueError(f"unknown task {task!r}")
+        if sections is None:
+            sections = int(os.environ.get("VLOG_AMD_SECTIONS", "") or 1)
+        if not 1 <= sections <= MAX_SECTIONS:
+            raise ValueError(f"sections must be between 1 and {MAX_SECTIONS}, got {sections}")
+        if sections_in_flight is not None and sections_in_flight < 1:
+            raise ValueError("sections_in_flight must be >= 1")
+        if sections > 1 and self.throughput:
+            raise ValueError("sections > 1 is the sequential mode's; throughput mode cuts the file its own way")
+        if sections > 1 and clip_timestamps not in ("0", [0], [0.0]):
+            raise ValueError("sections > 1 cannot be combined with clip_timestamps")
         if self.throughput:
             # opt-in throughput mode for the UNCHANGED worker (VLOG_AMD_THROUGHPUT=1): its call
             # transcribe(wav, language, task, beam_size=5, vad_filter=True) runs as BatchedInferencePipeline:
@@ -330,6 +364,8 @@ class WhisperModel:
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
                 language_detection_segments=language_detection_segments)
+        if sections > 1 and not isinstance(audio, np.ndarray):
+            audio = self._load_audio(audio)     # (the cuts without VAD are chosen on the samples)
         features, tokenizer, options, info, speech_chunks = self._prepare_file(
             audio, language=language, task=task, beam_size=beam_size, best_of=best_of, patience=patience,
             length_penalty=length_penalty, repetition_penalty=repetition_penalty,
@@ -345,11 +381,30 @@ class WhisperModel:
             hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hotwords,
             language_detection_threshold=language_detection_threshold,
             language_detection_segments=language_detection_segments)
-        gen = self.generate_segments(features, tokenizer, options)
+        bounds = self._plan_sections(audio, features, speech_chunks, sections) if sections > 1 else None
+        if bounds is not None:
+            options.section_frames = bounds
+        if bounds is not None and len(bounds) > 1:
+            gen = self._generate_sections(features, tokenizer, options, bounds, sections_in_flight or len(bounds))
+        else:
+            gen = self.generate_segments(features, tokenizer, options)
         if speech_chunks:
             from .vad import restore_speech_timestamps
             gen = restore_speech_timestamps(gen, speech_chunks, SAMPLE_RATE)
         return gen, info
+
+    def _plan_sections(self, audio: np.ndarray, features: torch.Tensor, speech_chunks, n: int) -> List[Tuple[int, int]]:
+        """plan_sections for one prepared file: at the VAD chunk joins when VAD ran, else at the quietest 20 ms frames
+        of the samples (wm_frame_energy)."""
+        content = features.shape[1] - 1
+        if speech_chunks is not None:
+            return plan_sections(content, n, joins=chunk_joins(speech_chunks))
+        if content < 2 * N_FRAMES:              # one section whatever the energies say
+            return plan_sections(content, n)
+        with self._lock:
+            energy = self.engine.frame_energy_db(
+                torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)), ENERGY_FRAME_MEL * HOP_LENGTH)
+        return plan_sections(content, n, energy=energy)
 
     def _prepare_file(self, audio, *, language, task, beam_size, best_of, patience, length_penalty, repetition_penalty,
                       no_repeat_ngram_size, temperature, compression_ratio_threshold, log_prob_threshold,
@@ -464,6 +519,108 @@ class WhisperModel:
             for d in out:
                 yield self._segment(d)
 
+    def _lockstep_round(self, batch, reserved: List[int], emit, features_of=None,
+                        shared: Optional[torch.Tensor] = None) -> None:
+        """One round of run_lockstep on the GPU, for transcribe_many (items = files, each with its own log-mel,
+        features_of(item)) and for the sections of one file (`shared`: the one log-mel every item reads).
+        batch: [(item, state, request)], entry i = cross slot i.  Reserve, ONE encoder call, cross_kv into slots
+        0..nb-1, the ragged first pass at temperatures[0] grouped by suppress list, the solo fallback passes, per-item
+        word alignment; emit(item, segment dicts).  reserved: [slots reserved by the caller's earlier rounds]."""
+        nb = len(batch)
+        opt0 = batch[0][1].options              # everything but the per-file prompt parts is common to the items
+        temps = opt0.temperatures
+        t0 = temps[0] if temps else 0.0
+        sampling = t0 > 0
+        per = (opt0.best_of if sampling else opt0.beam_size)
+        mit = int(round(opt0.max_initial_timestamp / self.time_precision))
+        sot = self.dims.specials.sot
+        with self._lock:                        # one lock scope per round: the slots hold this round's windows
+            self._use_cross_form(opt0.beam_size)      # (a no-op unless another caller changed the form)
+            if nb != reserved[0]:
+                self.engine.reserve(nb, max(nb * max(per, 1), 8))
+                reserved[0] = nb
+            if shared is not None:
+                # the items are ranges of one log-mel: the encoder reads each window where it lies
+                enc = self.engine.encode(shared, [req.seek for _, _, req in batch], [req.size for _, _, req in batch])
+            else:
+                # ONE encoder call over the round's windows, into slots 0..nb-1: window i's frames are copied to columns
+                # [i * 3000, i * 3000 + size) of one matrix (the encoder zero-pads each window to 3000 frames itself)
+                mel = torch.zeros((self.dims.n_mels, nb * N_FRAMES), device=features_of(batch[0][0]).device,
+                                  dtype=torch.float32)
+                for i, (f, _, req) in enumerate(batch):
+                    mel[:, i * N_FRAMES: i * N_FRAMES + req.size] = features_of(f)[:, req.seek: req.seek + req.size]
+                enc = self.engine.encode(mel, [i * N_FRAMES for i in range(nb)], [req.size for _, _, req in batch])
+            self.engine.cross_kv(enc, 0)
+
+            def first_pass(idx):
+                if sampling:
+                    # a sampled pass draws noise keyed on (seed, hypothesis index): a file's draws would depend on
+                    # its place in the round, so each window decodes alone, with generate_with_fallback's call
+                    return [self._generate(batch[i][2].prompt, batch[i][1].options, t0, batch[i][2].max_length,
+                                           batch[i][2].window, slot=i) for i in idx]
+                out: List[Optional[_GenOut]] = [None] * len(idx)
+                groups: dict = {}
+                for i in idx:                   # the suppress list is one per generate call
+                    groups.setdefault(tuple(batch[i][1].options.suppress_tokens), []).append(i)
+                for sup, members in groups.items():
+                    prompts = [batch[i][2].prompt for i in members]
+                    res, _ = self.engine.generate(
+                        members, prompts, beam_size=opt0.beam_size, patience=opt0.patience,
+                        length_penalty=opt0.length_penalty, max_length=[batch[i][2].max_length for i in members],
+                        temperature=t0, suppress_tokens=list(sup),
+                        suppress_blank=opt0.suppress_blank, max_initial_timestamp_index=mit,
+                        with_timestamps=not opt0.without_timestamps,
+                        sot_index=[p.index(sot) if sot in p else -1 for p in prompts], check_every=4,
+                        repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size)
+                    for i, r in zip(members, res):
+                        out[i] = _GenOut(r.tokens, r.score, r.no_speech_prob)
+                return out
+
+            def fallback_generate(i, t, seed):
+                _, state, req = batch[i]
+                return self._generate(req.prompt, state.options, t, req.max_length, seed, slot=i)
+
+            def align(i, current, size, last):
+                _, state, _ = batch[i]
+                o = state.options
+                return self.add_word_timestamps([current], state.tokenizer, size, o.prepend_punctuations,
+                                                o.append_punctuations, last, slots=[i])
+
+            decode_round_with(batch, first_pass, fallback_generate, align if opt0.word_timestamps else None, emit)
+
+    def _generate_sections(self, features: torch.Tensor, tokenizer: Tokenizer, options: TranscriptionOptions,
+                           bounds: Sequence[Tuple[int, int]], in_flight: int):
+        """The sectioned driver (transcribe(sections=N)): one SeekState per frame range of `bounds` (plan_sections),
+        decoded in lockstep with at most `in_flight` sections per round, as transcribe_many decodes files; the model
+        lock is held per round.  A generator: after every round it yields, in section order, the segments that are now
+        final (a section's segments wait until every earlier section has ended), with id 1, 2, ... in output order
+        and seek the absolute frame."""
+        content = features.shape[1] - 1
+        states: dict = {}
+        held: List[List[Segment]] = [[] for _ in bounds]
+        reserved = [0]
+        head, next_id = 0, 1
+
+        def open_section(k: int) -> SeekState:
+            states[k] = SeekState(content, tokenizer, options, self.max_length, self.frames_per_second,
+                                  clip_frames=bounds[k])
+            return states[k]
+
+        def decode_round(batch):
+            self._lockstep_round(batch, reserved, lambda k, out: held[k].extend(self._segment(d) for d in out),
+                                 shared=features)
+
+        for _ in iter_lockstep(len(bounds), in_flight, open_section, decode_round):
+            while head < len(bounds):
+                for seg in held[head]:
+                    seg.id = next_id
+                    next_id += 1
+                    yield seg
+                held[head] = []
+                if head not in states or states[head].next_request() is not None:
+                    break                       # the head section has windows left (or has not started yet)
+                head += 1
+
     def transcribe_many(self, audios: Sequence[Union[str, BinaryIO, np.ndarray]],
                         language: Union[None, str, Sequence[Optional[str]]] = None, task: str = "transcribe",
                         log_progress: bool = False, beam_size: int = 5, best_of: int = 5, patience: float = 1,
@@ -567,64 +724,8 @@ class WhisperModel:
         reserved = [0]
 
         def decode_round(batch):
-            nb = len(batch)
-            opt0 = batch[0][1].options              # everything but the per-file prompt parts is common to the files
-            temps = opt0.temperatures
-            t0 = temps[0] if temps else 0.0
-            sampling = t0 > 0
-            per = (opt0.best_of if sampling else opt0.beam_size)
-            mit = int(round(opt0.max_initial_timestamp / self.time_precision))
-            sot = self.dims.specials.sot
-            with self._lock:                        # one lock scope per round: the slots hold this round's windows
-                self._use_cross_form(opt0.beam_size)      # (a no-op unless another caller changed the form)
-                if nb != reserved[0]:
-                    self.engine.reserve(nb, max(nb * max(per, 1), 8))
-                    reserved[0] = nb
-                # ONE encoder call over the round's windows, into slots 0..nb-1: window i's frames are copied to columns
-                # [i * 3000, i * 3000 + size) of one matrix (the encoder zero-pads each window to 3000 frames itself)
-                mel = torch.zeros((self.dims.n_mels, nb * N_FRAMES), device=files[batch[0][0]][0].device,
-                                  dtype=torch.float32)
-                for i, (f, _, req) in enumerate(batch):
-                    mel[:, i * N_FRAMES: i * N_FRAMES + req.size] = files[f][0][:, req.seek: req.seek + req.size]
-                enc = self.engine.encode(mel, [i * N_FRAMES for i in range(nb)], [req.size for _, _, req in batch])
-                self.engine.cross_kv(enc, 0)
-
-                def first_pass(idx):
-                    if sampling:
-                        # a sampled pass draws noise keyed on (seed, hypothesis index): a file's draws would depend on
-                        # its place in the round, so each window decodes alone, with generate_with_fallback's call
-                        return [self._generate(batch[i][2].prompt, batch[i][1].options, t0, batch[i][2].max_length,
-                                               batch[i][2].window, slot=i) for i in idx]
-                    out: List[Optional[_GenOut]] = [None] * len(idx)
-                    groups: dict = {}
-                    for i in idx:                   # the suppress list is one per generate call
-                        groups.setdefault(tuple(batch[i][1].options.suppress_tokens), []).append(i)
-                    for sup, members in groups.items():
-                        prompts = [batch[i][2].prompt for i in members]
-                        res, _ = self.engine.generate(
-                            members, prompts, beam_size=opt0.beam_size, patience=opt0.patience,
-                            length_penalty=opt0.length_penalty, max_length=[batch[i][2].max_length for i in members],
-                            temperature=t0, suppress_tokens=list(sup),
-                            suppress_blank=opt0.suppress_blank, max_initial_timestamp_index=mit,
-                            with_timestamps=not opt0.without_timestamps,
-                            sot_index=[p.index(sot) if sot in p else -1 for p in prompts], check_every=4,
-                            repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size)
-                        for i, r in zip(members, res):
-                            out[i] = _GenOut(r.tokens, r.score, r.no_speech_prob)
-                    return out
-
-                def fallback_generate(i, t, seed):
-                    _, state, req = batch[i]
-                    return self._generate(req.prompt, state.options, t, req.max_length, seed, slot=i)
-
-                def align(i, current, size, last):
-                    _, state, _ = batch[i]
-                    o = state.options
-                    return self.add_word_timestamps([current], state.tokenizer, size, o.prepend_punctuations,
-                                                    o.append_punctuations, last, slots=[i])
-
-                decode_round_with(batch, first_pass, fallback_generate, align if opt0.word_timestamps else None,
-                                  lambda f, out: results[f].extend(self._segment(d) for d in out))
+            self._lockstep_round(batch, reserved, lambda f, out: results[f].extend(self._segment(d) for d in out),
+                                 features_of=lambda f: files[f][0])
 
         def close_file(f: int) -> None:
             files[f][0] = None                      # the file's log-mel leaves the device with its last window
