@@ -983,24 +983,68 @@ void debug_nan(wm_engine* e, float* logits, int rows, hipStream_t s) {
   }
 }
 
-// One graph-replayed decode loop's capture state (see generate)
+// The decode steps of one decode loop (generate, generate_rows, generate_rows_beam): eager, or a captured graph's replay.
+//
+// A decode step's launches are identical from step to step: every per-step quantity (tokens, positions,
+// lineage, done flags, sequence lengths) lives in device memory and is advanced by the select kernels, so
+// after one eager step (which sizes every scratch buffer) the step is captured once as a HIP graph and
+// replayed: one graph launch per step instead of ~11 kernel launches per layer.  Not with the event profiler
+// (its events are per launch) or the two-stream split.  The loop issues everything (steps, event passes, polls) on
+// `ds`: the replay stream, forked from `st` here and joined to it by finish(), or `st` itself without a graph.
+// Steps that run eagerly: the first, the one after rows_changed(), and the one after a buffer moved.
 struct StepGraph {
+  wm_engine* e;
+  hipStream_t st, ds;
+  const bool use;
+  int captures = 0;
   hipGraphExec_t exec = nullptr;
   bool capturing = false;
+  bool eager_next = true;                   // the next step runs eagerly (sizes scratch), the one after is captured
   long long gen = -1;                       // realloc_gen() at capture
+  StepGraph(wm_engine* e, hipStream_t st) : e(e), st(st), ds(st), use(e->dec_graph && !e->prof_on && !e->dec_split) {
+    if (!use) return;
+    if (!e->gst) {
+      HIP_OK(hipStreamCreateWithFlags(&e->gst, hipStreamNonBlocking));
+      HIP_OK(hipEventCreateWithFlags(&e->ev_g0, hipEventDisableTiming));
+      HIP_OK(hipEventCreateWithFlags(&e->ev_g1, hipEventDisableTiming));
+    }
+    HIP_OK(hipEventRecord(e->ev_g0, st));
+    HIP_OK(hipStreamWaitEvent(e->gst, e->ev_g0, 0));
+    ds = e->gst;
+  }
+  StepGraph(const StepGraph&) = delete;
+  // An exception leaves the loop through here: the stream leaves capture mode before the error is reported
+  ~StepGraph() {
+    if (capturing) {
+      hipGraph_t g = nullptr;
+      if (hipStreamEndCapture(ds, &g) == hipSuccess && g) (void)hipGraphDestroy(g);
+    }
+    drop();
+  }
   void drop() {
     if (exec) (void)hipGraphExecDestroy(exec);
     exec = nullptr;
   }
-  // false: buffers moved since the capture (the caller runs an eager step, which re-sizes, then captures again)
-  bool valid() const { return !exec || gen == realloc_gen(); }
-  template <class F> void run(hipStream_t ds, F&& step) {
+  // the pass's row count changed (compaction, an event pass): the captured graph no longer describes the step
+  void rows_changed() {
+    drop();
+    eager_next = true;
+  }
+  // One decode step: launches(stream) issues it.
+  template <class F> void step(F&& launches) {
+    if (exec && gen != realloc_gen()) rows_changed();   // a buffer the graph points into moved: an eager step re-sizes
+    if (!use || eager_next) {
+      eager_next = false;
+      launches(ds);
+      return;
+    }
     if (!exec) {
+      ++captures;
       hipGraph_t g = nullptr;
       gen = realloc_gen();
       HIP_OK(hipStreamBeginCapture(ds, hipStreamCaptureModeThreadLocal));
       capturing = true;
-      step();
+      launches(ds);
       capturing = false;
       HIP_OK(hipStreamEndCapture(ds, &g));
       const hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
@@ -1010,22 +1054,27 @@ struct StepGraph {
     }
     HIP_OK(hipGraphLaunch(exec, ds));
   }
-  void abort(hipStream_t ds) {            // leave the stream out of capture mode before reporting an error
-    if (capturing) {
-      hipGraph_t g = nullptr;
-      if (hipStreamEndCapture(ds, &g) == hipSuccess && g) (void)hipGraphDestroy(g);
-      capturing = false;
+  // The loop is over: `st` waits for the replay stream, and the graph's last replay completes before it is destroyed.
+  void finish() {
+    if (use) {
+      HIP_OK(hipEventRecord(e->ev_g1, ds));
+      HIP_OK(hipStreamWaitEvent(st, e->ev_g1, 0));
     }
-    drop();
+    if (exec) {
+      HIP_OK(hipStreamSynchronize(ds));
+      drop();
+    }
   }
 };
 
-// The per-window view of a call's prompts (ABI 4).  `ragged` is set when the caller passed any of h_prompt_lens /
-// h_sot_indices / h_max_lengths: the decode loops then take every length from here and the selection kernels from the
-// device tables; without it they run exactly the one-length code (len[w] = prompt_len for all w is never consulted).
+// The per-window view of a call's prompts (ABI 4): every window's prompt length, sot index and length limit, whether
+// the caller passed them per window or as one value.  `ragged` is set when the caller passed any of h_prompt_lens /
+// h_sot_indices / h_max_lengths, and means one thing: the selection kernels read the per-hypothesis device tables
+// (without it a call launches exactly the one-length kernels, with null table pointers).
 struct WinArgs {
   bool ragged = false;
   bool same_len = true;           // every window has the same prompt length (then the prefill keeps its grouping)
+  bool any_sot = false;           // some window has a sot index (the passes then produce no-speech logit rows)
   int Pmax = 0;                   // the longest prompt (scratch sizing, pass limit)
   int max_gen = 0;                // the most tokens any window may generate: max over w of ml[w] - len[w]
   std::vector<int> len, sot, ml;  // [W]
@@ -1044,6 +1093,8 @@ WinArgs window_args(wm_engine* e, const wm_generate_args* a) {
       if (a->h_prompts[i] < 0 || a->h_prompts[i] >= V) throw std::runtime_error("generate: prompt token out of the vocabulary");
     wa.Pmax = P;
     wa.max_gen = a->max_length - P;
+    wa.len.assign(W, P); wa.sot.assign(W, a->sot_index); wa.ml.assign(W, a->max_length);
+    wa.any_sot = a->sot_index >= 0;
     return wa;
   }
   if (P <= 0) throw std::runtime_error("generate: bad prompt_len/max_length");
@@ -1071,6 +1122,7 @@ WinArgs window_args(wm_engine* e, const wm_generate_args* a) {
     wa.Pmax = std::max(wa.Pmax, n);
     wa.max_gen = std::max(wa.max_gen, ml - n);
     if (n != wa.len[0]) wa.same_len = false;
+    wa.any_sot |= sot >= 0;
   }
   return wa;
 }
@@ -1092,6 +1144,175 @@ void upload_window_tables(wm_engine* e, const WinArgs& wa, int n_hyp, SearchPara
   if (bp) { bp->hyp_begin = sp->hyp_begin; bp->hyp_maxlen = sp->hyp_maxlen; }
 }
 
+// The beam selection's parameters beside `sp` (whose tables, record arrays and per-hypothesis length tables it shares)
+BeamParams beam_params(wm_engine* e, const wm_generate_args* a, const SearchParams& sp, int max_cand) {
+  BeamParams bp;
+  std::memset(&bp, 0, sizeof(bp));
+  bp.beam = a->beam_size; bp.max_cand = max_cand; bp.n_ctx = e->dm.n_text_ctx; bp.sample_begin = a->prompt_len;
+  bp.max_length = a->max_length;
+  bp.eot = e->dm.eot; bp.cand_tok = sp.cand_tok; bp.cand_lp = sp.cand_lp; bp.tokens = sp.tokens; bp.lin = e->d_lin.as<int>();
+  bp.seq_len = sp.seq_len; bp.cum = sp.cum; bp.done = sp.done; bp.row_tok = sp.row_tok; bp.row_pos = sp.row_pos;
+  bp.fin_tok = e->d_fin_tok.as<int>(); bp.fin_len = e->d_fin_len.as<int>(); bp.fin_cum = e->d_fin_cum.as<float>();
+  bp.n_fin = e->d_n_fin.as<int>(); bp.n_active = sp.n_active;
+  bp.hyp_begin = sp.hyp_begin; bp.hyp_maxlen = sp.hyp_maxlen;
+  if (sp.tok_lp) {
+    bp.tok_lp = sp.tok_lp;
+    bp.fin_lp = e->d_fin_lp.as<float>();
+  }
+  return bp;
+}
+
+float length_norm(const wm_generate_args* a, float cum, int n) {
+  return cum / std::pow((float)std::max(n, 1), a->length_penalty);
+}
+
+// Host copies of one window's finished list (entry i: tokens from the first generated one) or of its beam_size live
+// beams (entry b: the whole sequence, prompt included); entries are n_text_ctx apart in tok / lp.  lp: optional records.
+struct BeamView { const int* tok; const int* len; const float* cum; const float* lp; };
+struct BeamBest { const int* tok = nullptr; int len = 0; float cum = 0.f, score = -INFINITY; const float* lp = nullptr; };
+
+// The result of one window's beam search: the finished candidates (beam_select keeps n_fin within max_cand; clamped
+// here all the same), then, openai finalize, unfinished beams by sum_logprob until beam_size are ranked; the best
+// length-normalised score wins.  Pw: the window's own prompt length.
+BeamBest beam_best(const wm_generate_args* a, int C, int max_cand, int Pw, const BeamView& fin, int n_fin,
+                   const BeamView& beams) {
+  const int K = a->beam_size;
+  BeamBest best;
+  int n = 0;
+  auto offer = [&](const int* t, int len, float c, const float* r) {
+    const float s = length_norm(a, c, len);
+    if (s > best.score) { best.tok = t; best.len = len; best.cum = c; best.score = s; best.lp = r; }
+    ++n;
+  };
+  for (int i = 0; i < std::min(n_fin, max_cand); ++i)
+    offer(fin.tok + (size_t)i * C, fin.len[i], fin.cum[i], fin.lp ? fin.lp + (size_t)i * C : nullptr);
+  std::vector<int> order;
+  for (int b = 0; b < K; ++b)
+    if (beams.cum[b] > -INFINITY) order.push_back(b);
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return beams.cum[x] > beams.cum[y]; });
+  for (int b : order) {
+    if (n >= K) break;
+    offer(beams.tok + (size_t)b * C + Pw, beams.len[b] - Pw, beams.cum[b], beams.lp ? beams.lp + (size_t)b * C + Pw : nullptr);
+  }
+  return best;
+}
+
+// One window's result into the caller's arrays.  tok / lp / lpo start at the first generated token.  ns: the window's
+// no-speech probability (nullptr: the caller writes h_no_speech at its end).  Per-step records, when the call asks for
+// them: one per generated token, plus the final <|endoftext|> when the window ended on it (not at its length limit);
+// NaN where the decode form keeps no such record.
+void write_window_result(const wm_generate_args* a, const WinArgs& wa, int w, const int* tok, int n, float cum, float score,
+                         const float* ns, const float* lp, const float* lpo) {
+  const int ML = a->max_length;
+  if (n < 0 || n > ML) throw std::runtime_error("generate: window " + std::to_string(w) + " has no result");
+  for (int i = 0; i < n; ++i) a->h_tokens[(size_t)w * ML + i] = tok[i];
+  a->h_lengths[w] = n;
+  a->h_scores[w] = score;
+  if (a->h_cum_logprob) a->h_cum_logprob[w] = cum;
+  if (a->h_no_speech && ns) a->h_no_speech[w] = wa.sot[w] >= 0 ? *ns : 0.f;
+  if (a->h_token_logprobs) {
+    const int nr = std::min(ML, n + (wa.len[w] + n < wa.ml[w] ? 1 : 0));
+    for (int i = 0; i < nr; ++i) {
+      a->h_token_logprobs[(size_t)w * ML + i] = lp ? lp[i] : NAN;
+      if (a->h_token_logprobs_other) a->h_token_logprobs_other[(size_t)w * ML + i] = lpo ? lpo[i] : NAN;
+    }
+  }
+}
+
+void write_stats(const wm_generate_args* a, long long passes, long long row_steps, long long refills, int captures) {
+  if (a->h_steps) a->h_steps[0] = (int)passes;
+  if (a->h_stats) {
+    a->h_stats[0] = passes;
+    a->h_stats[1] = row_steps;
+    a->h_stats[2] = refills;
+    a->h_stats[3] = captures;
+  }
+}
+
+// The lists of one row-set event pass, carved from one int array: the host image e->h_ev (zero-filled here; it lives on
+// the engine until the next poll synchronises the stream) and, at the same offsets, its device copy d_ev:
+// ptok, ppos, phyp, psrc [np] | row set [nr] | logit rows [nr + nsot] | start slots (groups), windows [nst] | live count
+struct EventLists {
+  struct Ptrs { int *ptok, *ppos, *phyp, *psrc, *rh, *lr, *hs, *ws, *n_live; } h, d;
+  size_t n;
+  EventLists(wm_engine* e, int np, int nr, int nsot, int nst) : n((size_t)4 * np + 2 * nr + nsot + 2 * nst + 1) {
+    auto carve = [&](int* b) {
+      return Ptrs{b, b + np, b + 2 * np, b + 3 * np, b + 4 * np, b + 4 * np + nr, b + 4 * np + 2 * nr + nsot,
+                  b + 4 * np + 2 * nr + nsot + nst, b + 4 * np + 2 * nr + nsot + 2 * nst};
+    };
+    e->h_ev.assign(n, 0);
+    e->d_ev.ensure(n * 4);
+    h = carve(e->h_ev.data());
+    d = carve(e->d_ev.as<int>());
+  }
+  void upload(wm_engine* e, hipStream_t s) const {
+    HIP_OK(hipMemcpyAsync(e->d_ev.p, e->h_ev.data(), n * 4, hipMemcpyHostToDevice, s));
+  }
+};
+
+// What a row-set decode shares with its driver: the queue of windows, the current pass's rows, the counts for h_stats.
+struct RowSet {
+  int W = 0, next = 0;            // windows of the call; the next one to start
+  int nrows = 0;                  // rows of the current row set (event() sets it)
+  long long passes = 0, row_steps = 0, refills = 0;
+};
+struct RowSetRules {
+  int check;                      // decode passes between host polls
+  long long pass_limit;           // a generous bound against a stuck loop
+  int refill_min;                 // free units that make a refill worth its eager pass
+  int compact_8ths;               // compaction once the live units fall to this many eighths of the row set ...
+  bool compact;                   // ... if the call asked for it
+  int n_done;                     // hypothesis slots whose done flags a poll reads
+};
+
+// The row-set decode loop of generate_rows (unit: a row) and generate_rows_beam (unit: a group of beam_size rows).
+// The caller has listed the first windows' starts; then, every `check` passes, a poll (counters, done flags) and:
+//   ended(done, s)   marks the units whose window ended (beam: finalises them) -> {live units, units in the row set}
+//   rebuild(refill)  lists the next row set, starting windows in free units (refill) or dropping them (compaction)
+//                    -> windows started
+//   event(s)         one event pass over those lists (sets rs.nrows)
+//   step(s)          one decode step's launches
+template <class Ended, class Rebuild, class Event, class Step>
+void run_row_set(wm_engine* e, StepGraph& graph, RowSet& rs, const RowSetRules& r, Ended&& ended, Rebuild&& rebuild,
+                 Event&& event, Step&& step) {
+  std::vector<int> h_done(r.n_done);
+  int h_cnt[4] = {0, 0, 0, 0};                  // live hypotheses, error word
+  auto event_pass = [&] {
+    event(graph.ds);
+    ++rs.passes;
+    rs.row_steps += rs.nrows;
+  };
+  event_pass();
+  int k = 1;                                    // decode passes since the last host check
+  for (;;) {
+    if (k >= r.check) {
+      k = 0;
+      HIP_OK(hipMemcpyAsync(h_cnt, e->d_n_active.p, sizeof(h_cnt), hipMemcpyDeviceToHost, graph.ds));
+      HIP_OK(hipMemcpyAsync(h_done.data(), e->d_done.p, (size_t)r.n_done * 4, hipMemcpyDeviceToHost, graph.ds));
+      HIP_OK(hipStreamSynchronize(graph.ds));
+      check_decode_error(h_cnt + 1);
+      const std::pair<int, int> units = ended(h_done.data(), graph.ds);
+      const int n_live = units.first, n_free = units.second - n_live;
+      if (n_live == 0 && rs.next >= rs.W) break;
+      const bool refill = rs.next < rs.W && (n_free >= r.refill_min || n_live == 0);
+      const bool compact = rs.next >= rs.W && r.compact && n_live * 8 <= units.second * r.compact_8ths;
+      if (refill || compact) {
+        rs.refills += rebuild(refill);
+        const int before = rs.nrows;
+        event_pass();
+        if (rs.nrows != before) graph.rows_changed();
+        k = 1;
+        continue;
+      }
+    }
+    graph.step(step);
+    ++rs.passes;
+    rs.row_steps += rs.nrows;
+    ++k;
+    if (rs.passes > r.pass_limit) throw std::runtime_error("generate: decode did not terminate");
+  }
+}
+
 void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, hipStream_t st);
 void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, hipStream_t st);
 
@@ -1102,9 +1323,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   const int W = a->n_windows, P = a->prompt_len;
   if (W <= 0) return;
   const WinArgs wa = window_args(e, a);
-  const bool rag = wa.ragged;
-  auto plen = [&](int w) { return rag ? wa.len[w] : P; };
-  auto psot = [&](int w) { return rag ? wa.sot[w] : a->sot_index; };
+  const bool rag = wa.ragged, any_sot = wa.any_sot;
   if (!(a->repetition_penalty >= 0.f) || std::isinf(a->repetition_penalty))
     throw std::runtime_error("generate: repetition_penalty must be a finite value > 0 (0 or 1: off)");
   if (a->no_repeat_ngram_size < 0 || a->no_repeat_ngram_size > a->max_length)
@@ -1143,7 +1362,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   for (int h = 0; h < NH; ++h) {
     const int w = h / per;
     hyp_slot[h] = a->h_slots[w];
-    const int Pw = plen(w);
+    const int Pw = wa.len[w];
     seq_len[h] = Pw;
     for (int p = 0; p < Pw; ++p) tokens[(size_t)h * C + p] = a->h_prompts[(size_t)w * P + p];
     for (int p = 0; p < C; ++p) lin[(size_t)h * C + p] = (beam && p < Pw) ? w * per : h;
@@ -1187,7 +1406,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   std::vector<int> pf_cls(n_pf, 0), pf_order(n_pf);
   for (int i = 0; i < n_pf; ++i) {
     pf_order[i] = i;
-    const int g = gmul * plen(i * pf_per / per);
+    const int g = gmul * wa.len[i * pf_per / per];
     pf_cls[i] = (!rag || wa.same_len) ? g : (g <= 32 ? g : 0);
   }
   std::stable_sort(pf_order.begin(), pf_order.end(), [&](int x, int y) { return pf_cls[x] < pf_cls[y]; });
@@ -1195,14 +1414,9 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   for (int k = 0; k < n_pf; ++k) {
     const int i = pf_order[k];
     pf_at[i] = pf_off[k];
-    pf_off[k + 1] = pf_off[k] + plen(i * pf_per / per);
+    pf_off[k + 1] = pf_off[k] + wa.len[i * pf_per / per];
   }
   const int rows = pf_off[n_pf];
-  bool any_sot = a->sot_index >= 0;
-  if (rag) {
-    any_sot = false;
-    for (int w = 0; w < W; ++w) any_sot |= wa.sot[w] >= 0;
-  }
   const int nlog = any_sot ? 2 * NH : NH;
   const bool one_class = pf_cls[pf_order[0]] == pf_cls[pf_order[n_pf - 1]];
   // the pass's final LayerNorm gathers its nlog logit rows into s_hb rows [0, nlog): with the beam's shared
@@ -1213,15 +1427,15 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   {
     std::vector<int> rt(rows), rp(rows), rh(rows);
     for (int i = 0; i < n_pf; ++i)
-      for (int p = 0; p < plen(i * pf_per / per); ++p) {
+      for (int p = 0; p < wa.len[i * pf_per / per]; ++p) {
         const int r = pf_at[i] + p, h = i * pf_per;
         rt[r] = tokens[(size_t)h * C + p]; rp[r] = p; rh[r] = h;
       }
     for (int h = 0; h < NH; ++h) {            // a hypothesis' logits come from its row set's last prompt row
       const int i = h / pf_per;
-      lr[h] = pf_at[i] + plen(h / per) - 1;
+      lr[h] = pf_at[i] + wa.len[h / per] - 1;
       // (a ragged call's window without a sot index reads a row of its own; its no-speech result is dropped below)
-      if (any_sot) lr[NH + h] = pf_at[i] + std::max(0, psot(h / per));
+      if (any_sot) lr[NH + h] = pf_at[i] + std::max(0, wa.sot[h / per]);
     }
     HIP_OK(hipMemcpyAsync(e->d_prow_tok.p, rt.data(), rows * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(e->d_prow_pos.p, rp.data(), rows * 4, hipMemcpyHostToDevice, st));
@@ -1279,18 +1493,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
     sp.tok_lp = e->d_tok_lp.as<float>();
     if (!beam) sp.tok_lp_other = e->d_tok_lp_o.as<float>();
   }
-  BeamParams bp;
-  std::memset(&bp, 0, sizeof(bp));
-  bp.beam = a->beam_size; bp.max_cand = max_cand; bp.n_ctx = C; bp.sample_begin = P; bp.max_length = a->max_length;
-  bp.eot = m.eot; bp.cand_tok = sp.cand_tok; bp.cand_lp = sp.cand_lp; bp.tokens = sp.tokens; bp.lin = e->d_lin.as<int>();
-  bp.seq_len = sp.seq_len; bp.cum = sp.cum; bp.done = sp.done; bp.row_tok = sp.row_tok; bp.row_pos = sp.row_pos;
-  bp.fin_tok = e->d_fin_tok.as<int>(); bp.fin_len = e->d_fin_len.as<int>(); bp.fin_cum = e->d_fin_cum.as<float>();
-  bp.n_fin = e->d_n_fin.as<int>(); bp.n_active = sp.n_active;
-  bp.hyp_begin = sp.hyp_begin; bp.hyp_maxlen = sp.hyp_maxlen;
-  if (rec && beam) {
-    bp.tok_lp = e->d_tok_lp.as<float>();
-    bp.fin_lp = e->d_fin_lp.as<float>();
-  }
+  const BeamParams bp = beam_params(e, a, sp, max_cand);
 
   auto select = [&](int step) {
     sp.step = step;
@@ -1302,29 +1505,10 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   select(0);
   int steps = 1;
   long long row_steps = NH;                      // the prefill pass selects every hypothesis' first token
-  int captures = 0;
   const int max_steps = wa.max_gen;             // generated tokens (incl. the final one) <= max_length - P, per window
   const int check = std::max(1, a->check_every);
-  // A decode step's launches are identical from step to step: every per-step quantity (tokens, positions,
-  // lineage, done flags, sequence lengths) lives in device memory and is advanced by the select kernels, so
-  // after one eager step (which sizes every scratch buffer) the step is captured once as a HIP graph and
-  // replayed: one graph launch per step instead of ~11 kernel launches per layer.  Not with the event profiler
-  // (its events are per launch) or the two-stream split.  The replay stream is joined to `st` before every
-  // host poll and at the end.
-  const bool use_graph = e->dec_graph && !e->prof_on && !e->dec_split;
-  hipGraphExec_t gexec = nullptr;
-  bool capturing = false;
-  hipStream_t ds = st;
-  if (use_graph) {
-    if (!e->gst) {
-      HIP_OK(hipStreamCreateWithFlags(&e->gst, hipStreamNonBlocking));
-      HIP_OK(hipEventCreateWithFlags(&e->ev_g0, hipEventDisableTiming));
-      HIP_OK(hipEventCreateWithFlags(&e->ev_g1, hipEventDisableTiming));
-    }
-    HIP_OK(hipEventRecord(e->ev_g0, st));
-    HIP_OK(hipStreamWaitEvent(e->gst, e->ev_g0, 0));
-    ds = e->gst;
-  }
+  StepGraph graph(e, st);
+  const hipStream_t ds = graph.ds;
   // Beam compaction (a->compact): once the live windows' hypotheses fill <= 7/8 of the pass, the pass keeps only
   // them (row r -> hypothesis row_hyp[r], window groups stay contiguous); the beam state stays where it is, per
   // hypothesis (KV cache, lineage, tokens), so the rows' tokens / positions are gathered per pass (rows_fill) and
@@ -1352,64 +1536,39 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
     launch_logits_select(sp, nrows, s);
     if (beam) launch_beam_select(bp, W, s);
   };
-  StepGraph graph;
   int poll[4] = {0, 0, 0, 0};                   // live count + error word
-  bool eager_next = false;                      // the pass after a compaction runs eagerly (sizes scratch), then captures
   if (bcompact) h_bdone.resize(NH);
-  try {
-    for (int step = 1; step < max_steps; ++step) {
-      if ((step - 1) % check == 0) {
-        HIP_OK(hipMemcpyAsync(poll, e->d_n_active.p, sizeof(poll), hipMemcpyDeviceToHost, ds));
-        if (bcompact) HIP_OK(hipMemcpyAsync(h_bdone.data(), e->d_done.p, (size_t)NH * 4, hipMemcpyDeviceToHost, ds));
-        HIP_OK(hipStreamSynchronize(ds));
-        check_decode_error(poll + 1);
-        if (poll[0] <= 0) break;
-        // (beam passes are GEMM-row-bound at hundreds of rows, unlike the latency-bound greedy passes: compact at 7/8)
-        if (bcompact && poll[0] * 8 <= nrows * 7) {
-          // a finished window's hypotheses are all done (beam_select); keep the live windows' groups in order
-          int n = 0;
-          for (int r = 0; r < nrows; r += per) {
-            const int h0 = h_rows[r];
-            if (h_bdone[h0]) continue;
-            for (int b = 0; b < per; ++b) h_rows[n + b] = h0 + b;
-            n += per;
-          }
-          if (n > 0 && n < nrows) {
-            nrows = n;
-            HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, h_rows.data(), (size_t)nrows * 4, hipMemcpyHostToDevice, ds));
-            HIP_OK(hipStreamSynchronize(ds));
-            sp.row_hyp = e->d_row_hyp.as<int>();
-            graph.drop();
-            eager_next = true;
-          }
+  for (int step = 1; step < max_steps; ++step) {
+    if ((step - 1) % check == 0) {
+      HIP_OK(hipMemcpyAsync(poll, e->d_n_active.p, sizeof(poll), hipMemcpyDeviceToHost, ds));
+      if (bcompact) HIP_OK(hipMemcpyAsync(h_bdone.data(), e->d_done.p, (size_t)NH * 4, hipMemcpyDeviceToHost, ds));
+      HIP_OK(hipStreamSynchronize(ds));
+      check_decode_error(poll + 1);
+      if (poll[0] <= 0) break;
+      // (beam passes are GEMM-row-bound at hundreds of rows, unlike the latency-bound greedy passes: compact at 7/8)
+      if (bcompact && poll[0] * 8 <= nrows * 7) {
+        // a finished window's hypotheses are all done (beam_select); keep the live windows' groups in order
+        int n = 0;
+        for (int r = 0; r < nrows; r += per) {
+          const int h0 = h_rows[r];
+          if (h_bdone[h0]) continue;
+          for (int b = 0; b < per; ++b) h_rows[n + b] = h0 + b;
+          n += per;
+        }
+        if (n > 0 && n < nrows) {
+          nrows = n;
+          HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, h_rows.data(), (size_t)nrows * 4, hipMemcpyHostToDevice, ds));
+          HIP_OK(hipStreamSynchronize(ds));
+          sp.row_hyp = e->d_row_hyp.as<int>();
+          graph.rows_changed();
         }
       }
-      if (!graph.valid()) {                     // a buffer moved since the capture: one eager pass re-sizes
-        graph.drop();
-        eager_next = true;
-      }
-      if (!use_graph || step == 1 || eager_next) {
-        eager_next = false;
-        step_eager(step, use_graph ? ds : st);
-      } else {
-        if (!graph.exec) ++captures;
-        graph.run(ds, [&] { step_eager(step, ds); });
-      }
-      ++steps;
-      row_steps += nrows;
     }
-  } catch (...) {
-    graph.abort(ds);
-    throw;
+    graph.step([&](hipStream_t s) { step_eager(step, s); });
+    ++steps;
+    row_steps += nrows;
   }
-  if (use_graph) {
-    HIP_OK(hipEventRecord(e->ev_g1, ds));
-    HIP_OK(hipStreamWaitEvent(st, e->ev_g1, 0));
-  }
-  if (graph.exec) {
-    HIP_OK(hipStreamSynchronize(ds));          // the graph's last replay has completed before it is destroyed
-    graph.drop();
-  }
+  graph.finish();
 
   // ---- results
   std::vector<int> out_tok((size_t)NH * C), out_len(NH);
@@ -1443,70 +1602,27 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   }
   HIP_OK(hipStreamSynchronize(st));
   check_decode_error(poll + 1);
-  const float lp = a->length_penalty;
-  auto norm = [&](float c, int n) { return c / std::pow((float)std::max(n, 1), lp); };
-  const int ML = a->max_length;
   for (int w = 0; w < W; ++w) {
-    const int P = plen(w);                      // this window's own prompt length and length limit from here on
-    const int MLw = rag ? wa.ml[w] : ML;
-    int best_len = 0;
-    float best_cum = 0.f, best_score = -INFINITY;
-    const int* best_ptr = nullptr;
-    const float *best_lp = nullptr, *best_lpo = nullptr;   // records of the chosen hypothesis (first generated step)
+    const int Pw = wa.len[w], h0 = w * per;
+    BeamBest best;                              // (lp: the chosen hypothesis' records, from its first generated step)
+    const float* best_lpo = nullptr;
     if (beam) {
-      struct C2 { const int* t; int n; float c; const float* r; };
-      std::vector<C2> cands;
-      for (int i = 0; i < n_fin[w]; ++i) {
-        const size_t f = (size_t)w * max_cand + i;
-        cands.push_back({&fin_tok[f * C], fin_len[f], fin_cum[f], rec ? &fin_lp[f * C] : nullptr});
-      }
-      if ((int)cands.size() < a->beam_size) {       // openai finalize: add unfinished beams by sum_logprob
-        std::vector<int> order;
-        for (int b = 0; b < per; ++b)
-          if (out_cum[w * per + b] > -INFINITY) order.push_back(b);
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return out_cum[w * per + x] > out_cum[w * per + y]; });
-        for (int b : order) {
-          if ((int)cands.size() >= a->beam_size) break;
-          const int h = w * per + b;
-          cands.push_back({&out_tok[(size_t)h * C + P], out_len[h] - P, out_cum[h], rec ? &out_lp[(size_t)h * C + P] : nullptr});
-        }
-      }
-      for (const auto& c : cands) {
-        const float s = norm(c.c, c.n);
-        if (s > best_score) { best_score = s; best_len = c.n; best_cum = c.c; best_ptr = c.t; best_lp = c.r; }
-      }
+      const size_t f = (size_t)w * max_cand;
+      best = beam_best(a, C, max_cand, Pw, {&fin_tok[f * C], &fin_len[f], &fin_cum[f], rec ? &fin_lp[f * C] : nullptr}, n_fin[w],
+                       {&out_tok[(size_t)h0 * C], &out_len[h0], &out_cum[h0], rec ? &out_lp[(size_t)h0 * C] : nullptr});
     } else {
-      for (int j = 0; j < per; ++j) {
-        const int h = w * per + j;
-        const int n = out_len[h] - P;
-        const float s = norm(out_cum[h], n);
-        if (s > best_score) {
-          best_score = s; best_len = n; best_cum = out_cum[h]; best_ptr = &out_tok[(size_t)h * C + P];
-          if (rec) { best_lp = &out_lp[(size_t)h * C + P]; best_lpo = &out_lpo[(size_t)h * C + P]; }
+      for (int h = h0; h < h0 + per; ++h) {
+        const int n = out_len[h] - Pw;
+        const float s = length_norm(a, out_cum[h], n);
+        if (s > best.score) {
+          best.score = s; best.len = n; best.cum = out_cum[h]; best.tok = &out_tok[(size_t)h * C + Pw];
+          if (rec) { best.lp = &out_lp[(size_t)h * C + Pw]; best_lpo = &out_lpo[(size_t)h * C + Pw]; }
         }
       }
     }
-    for (int i = 0; i < best_len && i < ML; ++i) a->h_tokens[(size_t)w * ML + i] = best_ptr[i];
-    a->h_lengths[w] = best_len;
-    a->h_scores[w] = best_score;
-    if (a->h_cum_logprob) a->h_cum_logprob[w] = best_cum;
-    if (a->h_no_speech) a->h_no_speech[w] = psot(w) >= 0 ? ns[w * per] : 0.f;
-    if (rec) {
-      // one record per generated token, plus the final <|endoftext|> when the window ended on it
-      const int nr = std::min(ML, best_len + (P + best_len < MLw ? 1 : 0));
-      for (int i = 0; i < nr; ++i) {
-        a->h_token_logprobs[(size_t)w * ML + i] = best_lp ? best_lp[i] : NAN;
-        if (a->h_token_logprobs_other) a->h_token_logprobs_other[(size_t)w * ML + i] = best_lpo ? best_lpo[i] : NAN;
-      }
-    }
+    write_window_result(a, wa, w, best.tok, best.len, best.cum, best.score, &ns[h0], best.lp, best_lpo);
   }
-  if (a->h_stats) {
-    a->h_stats[0] = steps;
-    a->h_stats[1] = row_steps;
-    a->h_stats[2] = 0;
-    a->h_stats[3] = captures;
-  }
-  if (a->h_steps) a->h_steps[0] = steps;
+  write_stats(a, steps, row_steps, 0, graph.captures);
 }
 
 // Row-set decode: greedy (or sampling with one hypothesis) over W windows with at most R = max_rows in flight.
@@ -1527,16 +1643,8 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
   const int W = a->n_windows, P = a->prompt_len;
   const int R = a->max_rows > 0 ? std::min(a->max_rows, W) : W;
   const bool rec = a->h_token_logprobs != nullptr;
-  const int ML = a->max_length;
-  // ragged prompts: P stays the row stride of h_prompts; a window's own values come from wa
+  // P is the row stride of h_prompts; a window's own values come from wa
   const bool rag = wa.ragged;
-  auto plen = [&](int w) { return rag ? wa.len[w] : P; };
-  auto psot = [&](int w) { return rag ? wa.sot[w] : a->sot_index; };
-  bool any_sot = a->sot_index >= 0;
-  if (rag) {
-    any_sot = false;
-    for (int w = 0; w < W; ++w) any_sot |= wa.sot[w] >= 0;
-  }
   reserve(e, e->n_slots, R);
   // per-window inputs and outputs
   e->d_win_prompt.ensure((size_t)W * P * 4);
@@ -1582,9 +1690,8 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
   std::vector<int> row_hyp(R), hyp_win(R, -1);
   std::vector<char> live(R, 0);
   for (int r = 0; r < R; ++r) row_hyp[r] = r;
-  int nrows = R, next = 0;
-  long long passes = 0, row_steps = 0, refills = 0;
-  int captures = 0;
+  RowSet rs;
+  rs.W = W; rs.nrows = R;
 
   // One event pass.  `carry` per new row: the old row index of a carried live row, -1 for a row whose slot starts
   // a window (`starts`, in row order), -2 for an idle row (its slot ended; the selection skips it).
@@ -1592,56 +1699,49 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
   std::vector<std::pair<int, int>> starts;      // (slot, window)
   auto event = [&](hipStream_t s) {
     const int nr = (int)new_row_hyp.size(), nst = (int)starts.size();
-    const int nsot = any_sot ? nst : 0;
+    const int nsot = wa.any_sot ? nst : 0;
     int np = 0, n_live = 0, ks = 0;
     for (int c : carry) {
-      np += c >= 0 ? 1 : (c == -1 ? plen(starts[ks++].second) : 0);
+      np += c >= 0 ? 1 : (c == -1 ? wa.len[starts[ks++].second] : 0);
       n_live += c >= -1;
     }
-    // upload: ptok, ppos, phyp, psrc [np] | row set [nr] | logits rows [nr + nsot] | start slots, windows [nst] | live
-    std::vector<int>& u = e->h_ev;
-    u.assign((size_t)4 * np + 2 * nr + nsot + 2 * nst + 1, 0);
-    int* ptok = u.data(); int* ppos = ptok + np; int* phyp = ppos + np; int* psrc = phyp + np;
-    int* rh = psrc + np; int* lr = rh + nr; int* hs = lr + nr + nsot; int* ws = hs + nst;
-    ws[nst] = n_live;
+    const EventLists ev(e, np, nr, nsot, nst);
+    const EventLists::Ptrs &u = ev.h, &d = ev.d;
+    *u.n_live = n_live;
     int i = 0, k = 0;
     for (int r = 0; r < nr; ++r) {
-      rh[r] = new_row_hyp[r];
+      u.rh[r] = new_row_hyp[r];
       if (carry[r] >= 0) {
-        phyp[i] = new_row_hyp[r]; psrc[i] = carry[r];
-        lr[r] = i++;
+        u.phyp[i] = new_row_hyp[r]; u.psrc[i] = carry[r];
+        u.lr[r] = i++;
       } else if (carry[r] == -1) {
         const int h = starts[k].first, w = starts[k].second;
-        const int Pw = plen(w), sot = psot(w);
+        const int Pw = wa.len[w], sot = wa.sot[w];
         // (a window without a sot index in a call that has some: its row defaults to 0 and its result is dropped)
         for (int p = 0; p < Pw; ++p, ++i) {
-          ptok[i] = a->h_prompts[(size_t)w * P + p]; ppos[i] = p; phyp[i] = h; psrc[i] = -1;
-          if (p == sot) lr[nr + k] = i;
+          u.ptok[i] = a->h_prompts[(size_t)w * P + p]; u.ppos[i] = p; u.phyp[i] = h; u.psrc[i] = -1;
+          if (p == sot) u.lr[nr + k] = i;
         }
-        lr[r] = i - 1;                          // the last prompt position predicts the first token
-        hs[k] = h; ws[k] = w;
+        u.lr[r] = i - 1;                        // the last prompt position predicts the first token
+        u.hs[k] = h; u.ws[k] = w;
         ++k;
       } else {
-        lr[r] = 0;
+        u.lr[r] = 0;
       }
     }
-    e->d_ev.ensure(u.size() * 4);
-    int* du = e->d_ev.as<int>();
-    HIP_OK(hipMemcpyAsync(du, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
-    int* dptok = du; int* dppos = du + np; int* dphyp = du + 2 * np; int* dpsrc = du + 3 * np;
-    int* drh = du + 4 * np; int* dlr = drh + nr; int* dhs = dlr + nr + nsot; int* dws = dhs + nst;
+    ev.upload(e, s);
     // carried rows read token / position from the last selection's (old) row order before it is overwritten
-    launch_rows_fill(np, dpsrc, dptok, dppos, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
-    launch_hyp_start(nst, dhs, dws, e->d_win_prompt.as<int>(), P, e->d_win_slot.as<int>(), C, e->d_tokens.as<int>(),
+    launch_rows_fill(np, d.psrc, d.ptok, d.ppos, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
+    launch_hyp_start(nst, d.hs, d.ws, e->d_win_prompt.as<int>(), P, e->d_win_slot.as<int>(), C, e->d_tokens.as<int>(),
                      e->d_seq_len.as<int>(), e->d_done.as<int>(), e->d_cum.as<float>(), e->d_hyp_slot.as<int>(),
                      e->d_hyp_out.as<int>(), s, rag ? e->d_win_len.as<int>() : nullptr,
                      rag ? e->d_win_maxlen.as<int>() : nullptr, rag ? e->d_hyp_begin.as<int>() : nullptr,
                      rag ? e->d_hyp_maxlen.as<int>() : nullptr);
-    HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, drh, (size_t)nr * 4, hipMemcpyDeviceToDevice, s));
-    HIP_OK(hipMemcpyAsync(counters, dws + nst, 4, hipMemcpyDeviceToDevice, s));
-    decoder_pass(e, np, dptok, dppos, dphyp, e->d_done.as<int>(), nullptr, dlr, nr + nsot, logits, nullptr, 0, nullptr, 1, s,
-                 err);
-    if (nsot) launch_no_speech(logits + (size_t)nr * V, V, V, nsot, m.no_speech, e->d_res_ns.as<float>(), s, dws);
+    HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, d.rh, (size_t)nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(counters, d.n_live, 4, hipMemcpyDeviceToDevice, s));
+    decoder_pass(e, np, d.ptok, d.ppos, d.phyp, e->d_done.as<int>(), nullptr, d.lr, nr + nsot, logits, nullptr, 0, nullptr, 1,
+                 s, err);
+    if (nsot) launch_no_speech(logits + (size_t)nr * V, V, V, nsot, m.no_speech, e->d_res_ns.as<float>(), s, d.ws);
     debug_nan(e, logits, nr, s);
     {
       ProfScope ps(e, P_SELECT, s);
@@ -1650,120 +1750,59 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
     // host view of the new row set
     for (int r = 0; r < nr; ++r) row_hyp[r] = new_row_hyp[r];
     for (const auto& sw : starts) { hyp_win[sw.first] = sw.second; live[sw.first] = 1; }
-    nrows = nr;
-    ++passes;
-    row_steps += nr;
+    rs.nrows = nr;
   };
-
-  const bool use_graph = e->dec_graph && !e->prof_on && !e->dec_split;
-  hipStream_t ds = st;
-  if (use_graph) {
-    if (!e->gst) {
-      HIP_OK(hipStreamCreateWithFlags(&e->gst, hipStreamNonBlocking));
-      HIP_OK(hipEventCreateWithFlags(&e->ev_g0, hipEventDisableTiming));
-      HIP_OK(hipEventCreateWithFlags(&e->ev_g1, hipEventDisableTiming));
-    }
-    HIP_OK(hipEventRecord(e->ev_g0, st));
-    HIP_OK(hipStreamWaitEvent(e->gst, e->ev_g0, 0));
-    ds = e->gst;
-  }
-  auto step_eager = [&](hipStream_t s) {
-    decoder_pass(e, nrows, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), e->d_row_hyp.as<int>(), e->d_done.as<int>(),
-                 nullptr, nullptr, nrows, logits, nullptr, 0, nullptr, 1, s, err);
-    debug_nan(e, logits, nrows, s);
+  auto step = [&](hipStream_t s) {
+    decoder_pass(e, rs.nrows, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), e->d_row_hyp.as<int>(), e->d_done.as<int>(),
+                 nullptr, nullptr, rs.nrows, logits, nullptr, 0, nullptr, 1, s, err);
+    debug_nan(e, logits, rs.nrows, s);
     ProfScope ps(e, P_SELECT, s);
-    launch_logits_select(sp, nrows, s);
+    launch_logits_select(sp, rs.nrows, s);
+  };
+  // a slot whose hypothesis ended is free (its tokens are already in the per-window output tables)
+  auto ended = [&](const int* h_done, hipStream_t) {
+    int n_live = 0;
+    for (int r = 0; r < rs.nrows; ++r) {
+      const int h = row_hyp[r];
+      if (live[h] && h_done[h]) live[h] = 0;
+      n_live += live[h];
+    }
+    return std::make_pair(n_live, rs.nrows);
+  };
+  auto rebuild = [&](bool refill) {
+    carry.clear(); new_row_hyp.clear(); starts.clear();
+    for (int r = 0; r < rs.nrows; ++r) {
+      const int h = row_hyp[r];
+      if (live[h]) {
+        carry.push_back(r); new_row_hyp.push_back(h);
+      } else if (refill) {
+        if (rs.next < W) {
+          carry.push_back(-1); new_row_hyp.push_back(h); starts.push_back({h, rs.next++});
+        } else {
+          carry.push_back(-2); new_row_hyp.push_back(h);
+        }
+      }                                         // compact: ended rows leave the row set
+    }
+    return (int)starts.size();
   };
 
-  StepGraph graph;
-  bool graph_rows_changed = true;               // the next decode step runs eagerly (sizes scratch), then captures
-  const int check = std::max(1, a->check_every);
-  const int refill_min = std::max(1, R / 16);   // a refill pass runs eagerly: batch the starts
-  std::vector<int> h_done(R);
-  int h_cnt[4] = {0, 0, 0, 0};
-  // every window's tokens need at most max_length - P steps; a generous bound against a stuck loop
-  const long long pass_limit = (long long)(W / std::max(1, R) + 2) * (wa.max_gen + check + 2) + 16;
-  try {
-    // first pass: the first R windows start
-    carry.assign(R, -1);
-    new_row_hyp.resize(R);
-    starts.clear();
-    for (int r = 0; r < R; ++r) {
-      new_row_hyp[r] = r;
-      starts.push_back({r, next++});
-    }
-    event(ds);
-    int k = 1;                                  // decode passes since the last host check
-    for (;;) {
-      if (k >= check) {
-        k = 0;
-        HIP_OK(hipMemcpyAsync(h_cnt, counters, sizeof(h_cnt), hipMemcpyDeviceToHost, ds));
-        HIP_OK(hipMemcpyAsync(h_done.data(), e->d_done.p, (size_t)R * 4, hipMemcpyDeviceToHost, ds));
-        HIP_OK(hipStreamSynchronize(ds));
-        check_decode_error(h_cnt + 1);
-        int n_live = 0, n_free = 0;
-        for (int r = 0; r < nrows; ++r) {
-          const int h = row_hyp[r];
-          if (live[h] && h_done[h]) live[h] = 0;
-          n_live += live[h];
-        }
-        n_free = nrows - n_live;
-        if (n_live == 0 && next >= W) break;
-        const bool refill = next < W && (n_free >= refill_min || n_live == 0);
-        const bool compact = next >= W && a->compact && n_live * 8 <= nrows * row_compact_8ths();
-        if (refill || compact) {
-          carry.clear(); new_row_hyp.clear(); starts.clear();
-          for (int r = 0; r < nrows; ++r) {
-            const int h = row_hyp[r];
-            if (live[h]) {
-              carry.push_back(r); new_row_hyp.push_back(h);
-            } else if (refill) {
-              if (next < W) {
-                carry.push_back(-1); new_row_hyp.push_back(h); starts.push_back({h, next++});
-                ++refills;
-              } else {
-                carry.push_back(-2); new_row_hyp.push_back(h);
-              }
-            }                                   // compact: ended rows leave the row set
-          }
-          const int before = nrows;
-          event(ds);
-          if (nrows != before) {
-            graph.drop();
-            graph_rows_changed = true;
-          }
-          k = 1;
-          continue;
-        }
-      }
-      if (!graph.valid()) {                     // an event pass grew a buffer the captured graph points into
-        graph.drop();
-        graph_rows_changed = true;
-      }
-      if (!use_graph || graph_rows_changed) {
-        step_eager(ds);
-        graph_rows_changed = false;
-      } else {
-        if (!graph.exec) ++captures;
-        graph.run(ds, [&] { step_eager(ds); });
-      }
-      ++passes;
-      row_steps += nrows;
-      ++k;
-      if (passes > pass_limit) throw std::runtime_error("generate: decode did not terminate");
-    }
-  } catch (...) {
-    graph.abort(ds);
-    throw;
+  RowSetRules rules;
+  rules.check = std::max(1, a->check_every);
+  rules.refill_min = std::max(1, R / 16);       // a refill pass runs eagerly: batch the starts
+  // every window's tokens need at most max_length - P steps
+  rules.pass_limit = (long long)(W / std::max(1, R) + 2) * (wa.max_gen + rules.check + 2) + 16;
+  rules.compact = a->compact; rules.compact_8ths = row_compact_8ths();
+  rules.n_done = R;
+  // first pass: the first R windows start
+  carry.assign(R, -1);
+  new_row_hyp.resize(R);
+  for (int r = 0; r < R; ++r) {
+    new_row_hyp[r] = r;
+    starts.push_back({r, rs.next++});
   }
-  if (use_graph) {
-    HIP_OK(hipEventRecord(e->ev_g1, ds));
-    HIP_OK(hipStreamWaitEvent(st, e->ev_g1, 0));
-  }
-  if (graph.exec) {
-    HIP_OK(hipStreamSynchronize(ds));
-    graph.drop();
-  }
+  StepGraph graph(e, st);
+  run_row_set(e, graph, rs, rules, ended, rebuild, event, step);
+  graph.finish();
 
   // ---- results, by window
   std::vector<int> res_tok((size_t)W * C), res_len(W);
@@ -1772,6 +1811,7 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
   HIP_OK(hipMemcpyAsync(res_len.data(), e->d_res_len.p, (size_t)W * 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipMemcpyAsync(res_cum.data(), e->d_res_cum.p, (size_t)W * 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipMemcpyAsync(res_ns.data(), e->d_res_ns.p, (size_t)W * 4, hipMemcpyDeviceToHost, st));
+  int h_cnt[4] = {0, 0, 0, 0};
   HIP_OK(hipMemcpyAsync(h_cnt, counters, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
   if (rec) {
     res_lp.resize((size_t)W * C);
@@ -1781,30 +1821,10 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
   }
   HIP_OK(hipStreamSynchronize(st));
   check_decode_error(h_cnt + 1);
-  const float lp = a->length_penalty;
-  for (int w = 0; w < W; ++w) {
-    const int n = res_len[w];
-    if (n < 0 || n > ML) throw std::runtime_error("generate: window " + std::to_string(w) + " has no result");
-    for (int i = 0; i < n; ++i) a->h_tokens[(size_t)w * ML + i] = res_tok[(size_t)w * C + i];
-    a->h_lengths[w] = n;
-    a->h_scores[w] = res_cum[w] / std::pow((float)std::max(n, 1), lp);
-    if (a->h_cum_logprob) a->h_cum_logprob[w] = res_cum[w];
-    if (a->h_no_speech) a->h_no_speech[w] = psot(w) >= 0 ? res_ns[w] : 0.f;
-    if (rec) {
-      const int nr = std::min(ML, n + (plen(w) + n < (rag ? wa.ml[w] : ML) ? 1 : 0));
-      for (int i = 0; i < nr; ++i) {
-        a->h_token_logprobs[(size_t)w * ML + i] = res_lp[(size_t)w * C + i];
-        if (a->h_token_logprobs_other) a->h_token_logprobs_other[(size_t)w * ML + i] = res_lpo[(size_t)w * C + i];
-      }
-    }
-  }
-  if (a->h_steps) a->h_steps[0] = (int)passes;
-  if (a->h_stats) {
-    a->h_stats[0] = passes;
-    a->h_stats[1] = row_steps;
-    a->h_stats[2] = refills;
-    a->h_stats[3] = captures;
-  }
+  for (int w = 0; w < W; ++w)
+    write_window_result(a, wa, w, &res_tok[(size_t)w * C], res_len[w], res_cum[w], length_norm(a, res_cum[w], res_len[w]),
+                        &res_ns[w], rec ? &res_lp[(size_t)w * C] : nullptr, rec ? &res_lpo[(size_t)w * C] : nullptr);
+  write_stats(a, rs.passes, rs.row_steps, rs.refills, graph.captures);
 }
 
 // logit_rows (optional): the pass rows whose logits are wanted, in output order (overrides last_only)
@@ -1893,19 +1913,11 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
   const int W = a->n_windows, P = a->prompt_len, K = a->beam_size;
   const int G = std::max(1, std::min(a->max_rows / K, W));
   const int NH = G * K;
-  const int ML = a->max_length;
   const int max_cand = std::max(1, (int)std::lround(a->beam_size * a->patience));
   if (max_cand > 16) throw std::runtime_error("generate: beam_size * patience must be <= 16");
   if (a->h_token_logprobs) throw std::runtime_error("generate: per-step records need max_rows 0 with beam search");
-  // ragged prompts: P stays the row stride of h_prompts; a window's own values come from wa
+  // P is the row stride of h_prompts; a window's own values come from wa
   const bool rag = wa.ragged;
-  auto plen = [&](int w) { return rag ? wa.len[w] : P; };
-  auto psot = [&](int w) { return rag ? wa.sot[w] : a->sot_index; };
-  bool any_sot = a->sot_index >= 0;
-  if (rag) {
-    any_sot = false;
-    for (int w = 0; w < W; ++w) any_sot |= wa.sot[w] >= 0;
-  }
   reserve(e, e->n_slots, NH);
   e->d_win_prompt.ensure((size_t)W * P * 4);
   e->d_win_slot.ensure((size_t)W * 4);
@@ -1928,25 +1940,17 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
   SearchParams sp = search_params(e, a, logits, P);
   sp.mode = 1; sp.topk = K + 1;
   sp.row_hyp = e->d_row_hyp.as<int>();
-  BeamParams bp;
-  std::memset(&bp, 0, sizeof(bp));
-  bp.beam = K; bp.max_cand = max_cand; bp.n_ctx = C; bp.sample_begin = P; bp.max_length = ML;
-  bp.eot = m.eot; bp.cand_tok = sp.cand_tok; bp.cand_lp = sp.cand_lp; bp.tokens = sp.tokens; bp.lin = e->d_lin.as<int>();
-  bp.seq_len = sp.seq_len; bp.cum = sp.cum; bp.done = sp.done; bp.row_tok = sp.row_tok; bp.row_pos = sp.row_pos;
-  bp.fin_tok = e->d_fin_tok.as<int>(); bp.fin_len = e->d_fin_len.as<int>(); bp.fin_cum = e->d_fin_cum.as<float>();
-  bp.n_fin = e->d_n_fin.as<int>(); bp.n_active = sp.n_active;
+  BeamParams bp = beam_params(e, a, sp, max_cand);
   if (rag) upload_window_tables(e, wa, NH, &sp, &bp, st);
 
   // host view: the row set is a list of groups (K rows each, in order); group g decodes window gwin[g] while glive[g]
   std::vector<int> set(G), gwin(G, -1);
-  std::vector<char> glive(G, 0), wdone(W, 0);
+  std::vector<char> glive(G, 0);
   for (int g = 0; g < G; ++g) set[g] = g;
-  int next = 0, nfinal = 0;
-  long long passes = 0, row_steps = 0, refills = 0;
-  int captures = 0;
-  const float lp = a->length_penalty;
-  auto norm = [&](float c, int n) { return c / std::pow((float)std::max(n, 1), lp); };
-  // the finished groups' lists and beams -> their windows' results (openai finalize, as generate())
+  int nfinal = 0;
+  RowSet rs;
+  rs.W = W; rs.nrows = NH;
+  // the finished groups' lists and beams -> their windows' results (the ranking of generate(): beam_best)
   std::vector<int> f_tok, f_len, f_n, o_tok, o_len;
   std::vector<float> f_cum, o_cum;
   auto finalize = [&](const std::vector<int>& gs, hipStream_t s) {
@@ -1962,38 +1966,12 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
     HIP_OK(hipMemcpyAsync(o_cum.data(), e->d_cum.p, (size_t)NH * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     for (int g : gs) {
-      const int w = gwin[g];
-      const int P = plen(w);                    // the window's own prompt length
-      struct C2 { const int* t; int n; float c; };
-      std::vector<C2> cands;
-      for (int i = 0; i < std::min(f_n[g], max_cand); ++i) {
-        const size_t f = (size_t)g * max_cand + i;
-        cands.push_back({&f_tok[f * C], f_len[f], f_cum[f]});
-      }
-      if ((int)cands.size() < K) {
-        std::vector<int> order;
-        for (int b = 0; b < K; ++b)
-          if (o_cum[g * K + b] > -INFINITY) order.push_back(b);
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return o_cum[g * K + x] > o_cum[g * K + y]; });
-        for (int b : order) {
-          if ((int)cands.size() >= K) break;
-          const int h = g * K + b;
-          cands.push_back({&o_tok[(size_t)h * C + P], o_len[h] - P, o_cum[h]});
-        }
-      }
-      int best_len = 0;
-      float best_cum = 0.f, best_score = -INFINITY;
-      const int* best_ptr = nullptr;
-      for (const auto& c : cands) {
-        const float sc = norm(c.c, c.n);
-        if (sc > best_score) { best_score = sc; best_len = c.n; best_cum = c.c; best_ptr = c.t; }
-      }
-      if (best_len < 0 || best_len > ML) throw std::runtime_error("generate: window " + std::to_string(w) + " has no result");
-      for (int i = 0; i < best_len; ++i) a->h_tokens[(size_t)w * ML + i] = best_ptr[i];
-      a->h_lengths[w] = best_len;
-      a->h_scores[w] = best_score;
-      if (a->h_cum_logprob) a->h_cum_logprob[w] = best_cum;
-      wdone[w] = 1;
+      const int w = gwin[g], h0 = g * K;
+      const size_t f = (size_t)g * max_cand;
+      const BeamBest best = beam_best(a, C, max_cand, wa.len[w], {&f_tok[f * C], &f_len[f], &f_cum[f], nullptr}, f_n[g],
+                                      {&o_tok[(size_t)h0 * C], &o_len[h0], &o_cum[h0], nullptr});
+      // (no-speech values are read once, at the end)
+      write_window_result(a, wa, w, best.tok, best.len, best.cum, best.score, nullptr, nullptr, nullptr);
       ++nfinal;
       glive[g] = 0;
       gwin[g] = -1;
@@ -2003,7 +1981,6 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
   // One event pass: `starts` (group, window) begin in place; `nset` is the new row set (compaction drops groups).
   std::vector<int> nset;
   std::vector<std::pair<int, int>> starts;
-  int nrows = NH;
   // A starting group's P prompt rows are padded to K with copies of its last prompt row (same hypothesis, position
   // and token: identical self-KV writes), so every group of the pass holds K rows of one window and the
   // cross-attention keeps its per-window grouping (prompts longer than K rows: ungrouped rows).
@@ -2012,60 +1989,54 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
   const int ev_group = (!rag || wa.same_len) && wa.Pmax <= K ? K : 1;
   auto event = [&](hipStream_t s) {
     const int ng = (int)nset.size(), nr = ng * K, nst = (int)starts.size();
-    const int nsot = any_sot ? nst : 0;
+    const int nsot = wa.any_sot ? nst : 0;
     std::vector<int> start_of(G, -1);
     for (int k = 0; k < nst; ++k) start_of[starts[k].first] = k;
     int np = 0, n_live = 0;
     for (int g : nset) {
-      np += start_of[g] >= 0 ? (ev_group > 1 ? PR : plen(starts[start_of[g]].second)) : K;
+      np += start_of[g] >= 0 ? (ev_group > 1 ? PR : wa.len[starts[start_of[g]].second]) : K;
       n_live += (start_of[g] >= 0 || glive[g]) ? K : 0;
     }
-    std::vector<int>& u = e->h_ev;
-    u.assign((size_t)4 * np + 2 * nr + nsot + 2 * nst + 1, 0);
-    int* ptok = u.data(); int* ppos = ptok + np; int* phyp = ppos + np; int* psrc = phyp + np;
-    int* rh = psrc + np; int* lr = rh + nr; int* gsd = lr + nr + nsot; int* wsd = gsd + nst;
-    wsd[nst] = n_live;
+    const EventLists ev(e, np, nr, nsot, nst);
+    const EventLists::Ptrs &u = ev.h, &d = ev.d;
+    *u.n_live = n_live;
     int i = 0, r = 0;
     for (int g : nset) {
       const int h0 = g * K, k = start_of[g];
       if (k >= 0) {
         const int w = starts[k].second;
         int last = 0;
-        const int Pw = plen(w), sot = psot(w);
+        const int Pw = wa.len[w], sot = wa.sot[w];
         for (int p = 0; p < Pw; ++p, ++i) {
-          ptok[i] = a->h_prompts[(size_t)w * P + p]; ppos[i] = p; phyp[i] = h0; psrc[i] = -1;
-          if (p == sot) lr[nr + k] = i;
+          u.ptok[i] = a->h_prompts[(size_t)w * P + p]; u.ppos[i] = p; u.phyp[i] = h0; u.psrc[i] = -1;
+          if (p == sot) u.lr[nr + k] = i;
           last = i;
         }
         for (int p = Pw; ev_group > 1 && p < PR; ++p, ++i) {   // (grouped rows: every window has Pw = Pmax <= K)
-          ptok[i] = a->h_prompts[(size_t)w * P + Pw - 1]; ppos[i] = Pw - 1; phyp[i] = h0; psrc[i] = -1;
+          u.ptok[i] = a->h_prompts[(size_t)w * P + Pw - 1]; u.ppos[i] = Pw - 1; u.phyp[i] = h0; u.psrc[i] = -1;
         }
-        for (int b = 0; b < K; ++b, ++r) { rh[r] = h0 + b; lr[r] = last; }
-        gsd[k] = g; wsd[k] = w;
+        for (int b = 0; b < K; ++b, ++r) { u.rh[r] = h0 + b; u.lr[r] = last; }
+        u.hs[k] = g; u.ws[k] = w;
       } else {
         for (int b = 0; b < K; ++b, ++i, ++r) {
-          phyp[i] = h0 + b; psrc[i] = h0 + b;
-          rh[r] = h0 + b; lr[r] = i;
+          u.phyp[i] = h0 + b; u.psrc[i] = h0 + b;
+          u.rh[r] = h0 + b; u.lr[r] = i;
         }
       }
     }
-    e->d_ev.ensure(u.size() * 4);
-    int* du = e->d_ev.as<int>();
-    HIP_OK(hipMemcpyAsync(du, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
-    int* dptok = du; int* dppos = du + np; int* dphyp = du + 2 * np; int* dpsrc = du + 3 * np;
-    int* drh = du + 4 * np; int* dlr = drh + nr; int* dgs = dlr + nr + nsot; int* dws = dgs + nst;
+    ev.upload(e, s);
     // carried rows: token / position of their hypothesis from the last beam selection (hypothesis-indexed)
-    launch_rows_fill(np, dpsrc, dptok, dppos, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
-    launch_beam_start(nst, dgs, dws, K, e->d_win_prompt.as<int>(), P, e->d_win_slot.as<int>(), C, e->d_tokens.as<int>(),
+    launch_rows_fill(np, d.psrc, d.ptok, d.ppos, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
+    launch_beam_start(nst, d.hs, d.ws, K, e->d_win_prompt.as<int>(), P, e->d_win_slot.as<int>(), C, e->d_tokens.as<int>(),
                       e->d_lin.as<int>(), e->d_seq_len.as<int>(), e->d_done.as<int>(), e->d_cum.as<float>(),
                       e->d_hyp_slot.as<int>(), e->d_n_fin.as<int>(), s, rag ? e->d_win_len.as<int>() : nullptr,
                       rag ? e->d_win_maxlen.as<int>() : nullptr, rag ? e->d_hyp_begin.as<int>() : nullptr,
                       rag ? e->d_hyp_maxlen.as<int>() : nullptr);
-    HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, drh, (size_t)nr * 4, hipMemcpyDeviceToDevice, s));
-    HIP_OK(hipMemcpyAsync(counters, dws + nst, 4, hipMemcpyDeviceToDevice, s));
-    decoder_pass(e, np, dptok, dppos, dphyp, e->d_done.as<int>(), e->d_lin.as<int>(), dlr, nr + nsot, logits, nullptr, 0,
+    HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, d.rh, (size_t)nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(counters, d.n_live, 4, hipMemcpyDeviceToDevice, s));
+    decoder_pass(e, np, d.ptok, d.ppos, d.phyp, e->d_done.as<int>(), e->d_lin.as<int>(), d.lr, nr + nsot, logits, nullptr, 0,
                  nullptr, ev_group, s, err);
-    if (nsot) launch_no_speech(logits + (size_t)nr * V, V, V, nsot, m.no_speech, e->d_res_ns.as<float>(), s, dws);
+    if (nsot) launch_no_speech(logits + (size_t)nr * V, V, V, nsot, m.no_speech, e->d_res_ns.as<float>(), s, d.ws);
     debug_nan(e, logits, nr, s);
     {
       ProfScope ps(e, P_SELECT, s);
@@ -2074,109 +2045,51 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
     }
     for (const auto& gw : starts) { gwin[gw.first] = gw.second; glive[gw.first] = 1; }
     set = nset;
-    nrows = nr;
-    ++passes;
-    row_steps += nr;
+    rs.nrows = nr;
   };
-
-  const bool use_graph = e->dec_graph && !e->prof_on && !e->dec_split;
-  hipStream_t ds = st;
-  if (use_graph) {
-    if (!e->gst) {
-      HIP_OK(hipStreamCreateWithFlags(&e->gst, hipStreamNonBlocking));
-      HIP_OK(hipEventCreateWithFlags(&e->ev_g0, hipEventDisableTiming));
-      HIP_OK(hipEventCreateWithFlags(&e->ev_g1, hipEventDisableTiming));
-    }
-    HIP_OK(hipEventRecord(e->ev_g0, st));
-    HIP_OK(hipStreamWaitEvent(e->gst, e->ev_g0, 0));
-    ds = e->gst;
-  }
-  auto step_eager = [&](hipStream_t s) {
-    launch_rows_fill(nrows, e->d_row_hyp.as<int>(), e->d_prow_tok.as<int>(), e->d_prow_pos.as<int>(),
+  auto step = [&](hipStream_t s) {
+    launch_rows_fill(rs.nrows, e->d_row_hyp.as<int>(), e->d_prow_tok.as<int>(), e->d_prow_pos.as<int>(),
                      e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
-    decoder_pass(e, nrows, e->d_prow_tok.as<int>(), e->d_prow_pos.as<int>(), e->d_row_hyp.as<int>(), e->d_done.as<int>(),
-                 e->d_lin.as<int>(), nullptr, nrows, logits, nullptr, 0, nullptr, K, s, err);
-    debug_nan(e, logits, nrows, s);
+    decoder_pass(e, rs.nrows, e->d_prow_tok.as<int>(), e->d_prow_pos.as<int>(), e->d_row_hyp.as<int>(), e->d_done.as<int>(),
+                 e->d_lin.as<int>(), nullptr, rs.nrows, logits, nullptr, 0, nullptr, K, s, err);
+    debug_nan(e, logits, rs.nrows, s);
     ProfScope ps(e, P_SELECT, s);
-    launch_logits_select(sp, nrows, s);
+    launch_logits_select(sp, rs.nrows, s);
     launch_beam_select(bp, G, s);
   };
-
-  StepGraph graph;
-  bool graph_rows_changed = true;
-  const int check = std::max(1, a->check_every);
-  const int refill_min = std::max(1, G / 16);
-  std::vector<int> h_done(NH);
-  int h_cnt[4] = {0, 0, 0, 0};
-  const long long pass_limit = (long long)(W / G + 2) * (wa.max_gen + check + 2) + 16;
-  try {
-    nset = set;
-    starts.clear();
-    for (int g = 0; g < G; ++g) starts.push_back({g, next++});
-    event(ds);
-    int k = 1;
-    for (;;) {
-      if (k >= check) {
-        k = 0;
-        HIP_OK(hipMemcpyAsync(h_cnt, counters, sizeof(h_cnt), hipMemcpyDeviceToHost, ds));
-        HIP_OK(hipMemcpyAsync(h_done.data(), e->d_done.p, (size_t)NH * 4, hipMemcpyDeviceToHost, ds));
-        HIP_OK(hipStreamSynchronize(ds));
-        check_decode_error(h_cnt + 1);
-        std::vector<int> ended;
-        for (int g = 0; g < G; ++g)
-          if (glive[g] && h_done[g * K]) ended.push_back(g);
-        finalize(ended, ds);
-        int n_live = 0, n_free = 0;
-        for (int g : set) { n_live += glive[g]; n_free += !glive[g]; }
-        if (n_live == 0 && next >= W) break;
-        const bool refill = next < W && (n_free >= refill_min || n_live == 0);
-        const bool compact = a->compact && next >= W && n_live * 8 <= (int)set.size() * 7;   // opt-in, as the header says
-        if (refill || compact) {
-          nset.clear(); starts.clear();
-          for (int g : set) {
-            if (glive[g]) nset.push_back(g);
-            else if (refill && next < W) { nset.push_back(g); starts.push_back({g, next++}); ++refills; }
-            else if (refill) nset.push_back(g);       // idle until compaction (rows stay in place)
-          }
-          const int before = nrows;
-          event(ds);
-          if (nrows != before) {
-            graph.drop();
-            graph_rows_changed = true;
-          }
-          k = 1;
-          continue;
-        }
-      }
-      if (!graph.valid()) {
-        graph.drop();
-        graph_rows_changed = true;
-      }
-      if (!use_graph || graph_rows_changed) {
-        step_eager(ds);
-        graph_rows_changed = false;
-      } else {
-        if (!graph.exec) ++captures;
-        graph.run(ds, [&] { step_eager(ds); });
-      }
-      ++passes;
-      row_steps += nrows;
-      ++k;
-      if (passes > pass_limit) throw std::runtime_error("generate: decode did not terminate");
+  // a group whose window beam_select ended is finalised and free
+  auto ended = [&](const int* h_done, hipStream_t s) {
+    std::vector<int> gs;
+    for (int g = 0; g < G; ++g)
+      if (glive[g] && h_done[g * K]) gs.push_back(g);
+    finalize(gs, s);
+    int n_live = 0;
+    for (int g : set) n_live += glive[g];
+    return std::make_pair(n_live, (int)set.size());
+  };
+  auto rebuild = [&](bool refill) {
+    nset.clear(); starts.clear();
+    for (int g : set) {
+      if (glive[g]) nset.push_back(g);
+      else if (refill && rs.next < W) { nset.push_back(g); starts.push_back({g, rs.next++}); }
+      else if (refill) nset.push_back(g);       // idle until compaction (rows stay in place)
     }
-  } catch (...) {
-    graph.abort(ds);
-    throw;
-  }
-  if (use_graph) {
-    HIP_OK(hipEventRecord(e->ev_g1, ds));
-    HIP_OK(hipStreamWaitEvent(st, e->ev_g1, 0));
-  }
-  if (graph.exec) {
-    HIP_OK(hipStreamSynchronize(ds));
-    graph.drop();
-  }
+    return (int)starts.size();
+  };
+
+  RowSetRules rules;
+  rules.check = std::max(1, a->check_every);
+  rules.refill_min = std::max(1, G / 16);
+  rules.pass_limit = (long long)(W / G + 2) * (wa.max_gen + rules.check + 2) + 16;
+  rules.compact = a->compact; rules.compact_8ths = 7;   // opt-in, as the header says; beam passes are GEMM-row-bound
+  rules.n_done = NH;
+  nset = set;
+  for (int g = 0; g < G; ++g) starts.push_back({g, rs.next++});
+  StepGraph graph(e, st);
+  run_row_set(e, graph, rs, rules, ended, rebuild, event, step);
+  graph.finish();
   std::vector<float> res_ns(W);
+  int h_cnt[4] = {0, 0, 0, 0};
   HIP_OK(hipMemcpyAsync(res_ns.data(), e->d_res_ns.p, (size_t)W * 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipMemcpyAsync(h_cnt, counters, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
@@ -2184,14 +2097,8 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
   if (nfinal != W) throw std::runtime_error("generate: beam row-set finished " + std::to_string(nfinal) + " of " +
                                             std::to_string(W) + " windows");
   for (int w = 0; w < W; ++w)
-    if (a->h_no_speech) a->h_no_speech[w] = psot(w) >= 0 ? res_ns[w] : 0.f;
-  if (a->h_steps) a->h_steps[0] = (int)passes;
-  if (a->h_stats) {
-    a->h_stats[0] = passes;
-    a->h_stats[1] = row_steps;
-    a->h_stats[2] = refills;
-    a->h_stats[3] = captures;
-  }
+    if (a->h_no_speech) a->h_no_speech[w] = wa.sot[w] >= 0 ? res_ns[w] : 0.f;
+  write_stats(a, rs.passes, rs.row_steps, rs.refills, graph.captures);
 }
 
 void align(wm_engine* e, int slot, int sot_len, const int* h_sot, int n_text, const int* h_text, int num_frames,
