@@ -276,6 +276,25 @@ int wm_align_batch(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t sot_
 /* DTW alone on a device cost matrix d_cost[n][m] (openai dtw semantics); path as for wm_align. */
 int wm_dtw(wm_engine* e, const float* d_cost, int32_t n, int32_t m, int32_t* h_text_idx, int32_t* h_time_idx,
            int32_t* h_path_len, void* stream);
+/* The open-end form of wm_dtw (forced alignment: a window may be handed more text rows than its audio holds, so
+ * the path may stop at any row).  The same recurrence, f32 arithmetic, tie rules and trace as wm_dtw; then
+ * R = the smallest i in [1, n] that minimises cost[i][m], the backtrace starts at (R, m) instead of (n, m), and
+ * *h_rows = R ("rows reached": the path visits rows 0 .. R-1 and every column).  No length normalisation: the
+ * alignment matrix is the negated per-frame z-score, every column has mean 0 over the rows, so rows whose audio
+ * lies beyond the window add positive cost and stopping early leaves negative cost unused.  Path capacity n + m.
+ * A minimum that is not finite (NaN or infinity in d_cost) fails the call with "non-finite alignment cost"
+ * and writes nothing.  (Added without an ABI bump: new entry points only.) */
+int wm_dtw_open(wm_engine* e, const float* d_cost, int32_t n, int32_t m, int32_t* h_text_idx, int32_t* h_time_idx,
+                int32_t* h_path_len, int32_t* h_rows, void* stream);
+/* wm_align_batch with the open-end DTW (wm_dtw_open) in place of the closed one: the same teacher-forced pass,
+ * capture, text-token probabilities and matrix kernels; item i's path ends at row h_rows[i] - 1 of its
+ * n_text_i + 1 rows (h_rows [n]; h_rows[i] == n_text_i + 1 gives wm_align_batch's path).  Path capacity per item
+ * stays n_text_i + 1 + num_frames_i / 2.  An item whose minimum end cost is not finite fails the call, naming it. */
+int wm_align_open_batch(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t sot_len, const int32_t* h_sot,
+                        const int32_t* h_text_off, const int32_t* h_text, const int32_t* h_num_frames,
+                        const int32_t* h_heads, int32_t n_heads, int32_t median_filter_width, float* h_probs,
+                        const int64_t* h_path_off, int32_t* h_text_idx, int32_t* h_time_idx, int32_t* h_path_len,
+                        int32_t* h_rows, void* stream);
 
 /* Encoder self-attention kernel alone (diagnostics / parity tests; wm_encode runs it per layer):
  * d_qkv bf16 [B][T][3 n_state] (q | k | v, head h at columns h*64), d_out bf16 [B][T][n_state]. */

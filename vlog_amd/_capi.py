@@ -20,6 +20,7 @@ SYMBOLS = (
     "wm_detect_language", "wm_frame_energy", "wm_pcm_from_s16", "wm_vad_probs", "wm_cross_fp8_quantize", "wm_align", "wm_align_batch", "wm_dtw", "wm_device_bytes", "wm_profile_classes", "wm_profile_name", "wm_profile", "wm_profile_select",
     "wm_profile_read", "wm_set_option", "wm_get_option", "wm_encoder_attention",
     "wm_resample_plan", "wm_resample_taps", "wm_resample",
+    "wm_dtw_open", "wm_align_open_batch",
 )
 
 
@@ -93,6 +94,10 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                                      C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(C.c_float), C.POINTER(i64),
                                      C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]),
         "wm_dtw": (C.c_int, [vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]),
+        "wm_dtw_open": (C.c_int, [vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]),
+        "wm_align_open_batch": (C.c_int, [vp, i32, C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                                          C.POINTER(i32), C.POINTER(i32), i32, i32, C.POINTER(C.c_float), C.POINTER(i64),
+                                          C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]),
         "wm_device_bytes": (i64, [vp]),
         "wm_profile_classes": (i32, []),
         "wm_profile_name": (C.c_char_p, [i32]),

@@ -238,9 +238,18 @@ __global__ __launch_bounds__(256) void align_zmed_kernel(const float* __restrict
 }
 
 // cost [(N+1)][(M+1)] f32, trace [(N+1)][(M+1)] int8 scratch; x [N][M]; out path (text, time) reversed order fixed
+//
+// OPEN = false is openai's DTW: the backtrace starts at (N, M).  OPEN = true is the open-end form (forced
+// alignment hands a window more text rows than its audio holds, so the path may stop at any row): the same
+// recurrence, f32 arithmetic, tie rules and trace; then R = the smallest i in [1, N] that minimises cost[i][M]
+// (a block-wide argmin over the last column: 256 threads strided over the rows, wave shuffles, then the four
+// waves' results through LDS), the backtrace starts at (R, M), and R goes to out_rows ("rows reached").  A
+// minimum that is not finite (a NaN or an infinity in x) gives R = 0 and an empty path.
+template <bool OPEN>
 __device__ __forceinline__ void dtw_kernel_body(const float* __restrict__ x, int N, int M, float* __restrict__ cost,
                                                 signed char* __restrict__ trace, int* __restrict__ out_i,
-                                                int* __restrict__ out_j, int* __restrict__ out_len) {
+                                                int* __restrict__ out_j, int* __restrict__ out_len,
+                                                int* __restrict__ out_rows) {
   const int tid = threadIdx.x;
   const long long W = M + 1;
   for (long long k = tid; k < (long long)(N + 1) * W; k += 256) {
@@ -266,8 +275,38 @@ __device__ __forceinline__ void dtw_kernel_body(const float* __restrict__ x, int
     }
     __syncthreads();
   }
+  int R = N;
+  if constexpr (OPEN) {
+    __shared__ float red_v[4];
+    __shared__ int red_i[4], red_nan[4];
+    float bv = INFINITY;
+    int bi = 0x7fffffff, bnan = 0;
+    for (int i = 1 + tid; i <= N; i += 256) {       // ascending rows and a strict <: ties keep the smaller i
+      const float v = cost[i * W + M];
+      bnan |= (v != v);
+      if (v < bv) { bv = v; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      bnan |= __shfl_xor(bnan, o, 64);
+      if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if ((tid & 63) == 0) { red_v[tid >> 6] = bv; red_i[tid >> 6] = bi; red_nan[tid >> 6] = bnan; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < 4; ++w) {
+        bnan |= red_nan[w];
+        if (red_v[w] < bv || (red_v[w] == bv && red_i[w] < bi)) { bv = red_v[w]; bi = red_i[w]; }
+      }
+      R = (bnan || !(fabsf(bv) < INFINITY)) ? 0 : bi;
+      *out_rows = R;
+    }
+  }
   if (tid == 0) {
-    int i = N, j = M, n = 0;
+    int i = R, j = M, n = 0;
+    if (OPEN && R == 0) j = 0;                      // no finite end row: an empty path
     while (i > 0 || j > 0) {
       out_i[n] = i - 1;
       out_j[n] = j - 1;
@@ -289,7 +328,14 @@ __device__ __forceinline__ void dtw_kernel_body(const float* __restrict__ x, int
 __global__ __launch_bounds__(256) void dtw_kernel(const float* __restrict__ x, int N, int M, float* __restrict__ cost,
                                                   signed char* __restrict__ trace, int* __restrict__ out_i,
                                                   int* __restrict__ out_j, int* __restrict__ out_len) {
-  dtw_kernel_body(x, N, M, cost, trace, out_i, out_j, out_len);
+  dtw_kernel_body<false>(x, N, M, cost, trace, out_i, out_j, out_len, nullptr);
+}
+
+__global__ __launch_bounds__(256) void dtw_open_kernel(const float* __restrict__ x, int N, int M, float* __restrict__ cost,
+                                                       signed char* __restrict__ trace, int* __restrict__ out_i,
+                                                       int* __restrict__ out_j, int* __restrict__ out_len,
+                                                       int* __restrict__ out_rows) {
+  dtw_kernel_body<true>(x, N, M, cost, trace, out_i, out_j, out_len, out_rows);
 }
 
 void launch_token_probs(const float* logits, int rows, int V, int eot, const int* next_tok, float* out, hipStream_t st) {
@@ -381,6 +427,12 @@ void launch_dtw(const float* x, int N, int M, float* cost, signed char* trace, i
   WM_LAUNCH_CHECK("dtw_kernel");
 }
 
+void launch_dtw_open(const float* x, int N, int M, float* cost, signed char* trace, int* out_i, int* out_j, int* out_len,
+                     int* out_rows, hipStream_t st) {
+  hipLaunchKernelGGL(dtw_open_kernel, dim3(1), dim3(256), 0, st, x, N, M, cost, trace, out_i, out_j, out_len, out_rows);
+  WM_LAUNCH_CHECK("dtw_open_kernel");
+}
+
 // Batched DTW: one workgroup per matrix (item b reads x + x_off[b], an N[b] x M[b] matrix; its cost / trace
 // scratch starts at c_off[b], (N+1) x (M+1) cells; its path goes to out + p_off[b], capacity N + M).  The same
 // wavefront and backtrace as dtw_kernel, so every item's path is bit-identical to a dtw_kernel launch on it.
@@ -391,8 +443,20 @@ __global__ __launch_bounds__(256) void dtw_batch_kernel(const float* __restrict_
                                                         int* __restrict__ out_j, const long long* __restrict__ p_off,
                                                         int* __restrict__ out_len) {
   const int b = blockIdx.x;
-  dtw_kernel_body(x + x_off[b], Ns[b], Ms[b], cost_all + c_off[b], trace_all + c_off[b], out_i + p_off[b],
-                  out_j + p_off[b], out_len + b);
+  dtw_kernel_body<false>(x + x_off[b], Ns[b], Ms[b], cost_all + c_off[b], trace_all + c_off[b], out_i + p_off[b],
+                         out_j + p_off[b], out_len + b, nullptr);
+}
+
+// The open-end form of dtw_batch_kernel: the same tables, plus rows reached per item.
+__global__ __launch_bounds__(256) void dtw_open_batch_kernel(const float* __restrict__ x, const long long* __restrict__ x_off,
+                                                             const int* __restrict__ Ns, const int* __restrict__ Ms,
+                                                             float* __restrict__ cost_all, signed char* __restrict__ trace_all,
+                                                             const long long* __restrict__ c_off, int* __restrict__ out_i,
+                                                             int* __restrict__ out_j, const long long* __restrict__ p_off,
+                                                             int* __restrict__ out_len, int* __restrict__ out_rows) {
+  const int b = blockIdx.x;
+  dtw_kernel_body<true>(x + x_off[b], Ns[b], Ms[b], cost_all + c_off[b], trace_all + c_off[b], out_i + p_off[b],
+                        out_j + p_off[b], out_len + b, out_rows + b);
 }
 
 void launch_dtw_batch(const float* x, const long long* x_off, const int* Ns, const int* Ms, float* cost,
@@ -402,4 +466,13 @@ void launch_dtw_batch(const float* x, const long long* x_off, const int* Ns, con
   hipLaunchKernelGGL(dtw_batch_kernel, dim3(n), dim3(256), 0, st, x, x_off, Ns, Ms, cost, trace, c_off, out_i, out_j,
                      p_off, out_len);
   WM_LAUNCH_CHECK("dtw_batch_kernel");
+}
+
+void launch_dtw_open_batch(const float* x, const long long* x_off, const int* Ns, const int* Ms, float* cost,
+                           signed char* trace, const long long* c_off, int* out_i, int* out_j, const long long* p_off,
+                           int* out_len, int* out_rows, int n, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(dtw_open_batch_kernel, dim3(n), dim3(256), 0, st, x, x_off, Ns, Ms, cost, trace, c_off, out_i, out_j,
+                     p_off, out_len, out_rows);
+  WM_LAUNCH_CHECK("dtw_open_batch_kernel");
 }

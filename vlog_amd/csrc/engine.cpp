@@ -66,6 +66,9 @@ int align_get_fused();
 void launch_dtw(const float*, int, int, float*, signed char*, int*, int*, int*, hipStream_t);
 void launch_dtw_batch(const float*, const long long*, const int*, const int*, float*, signed char*, const long long*,
                       int*, int*, const long long*, int*, int, hipStream_t);
+void launch_dtw_open(const float*, int, int, float*, signed char*, int*, int*, int*, int*, hipStream_t);
+void launch_dtw_open_batch(const float*, const long long*, const int*, const int*, float*, signed char*, const long long*,
+                           int*, int*, const long long*, int*, int*, int, hipStream_t);
 
 // Kernel classes timed by the built-in profiler (wm_profile / wm_profile_read).
 enum ProfClass {
@@ -1882,17 +1885,29 @@ void forward(wm_engine* e, int n_seq, const int* h_slots, int S, const int* h_to
   HIP_OK(hipStreamSynchronize(st));
 }
 
-void dtw_run(wm_engine* e, const float* d_x, int N, int M, int* h_i, int* h_j, int* h_len, hipStream_t st) {
+// h_rows null: the closed DTW (the path ends at (N, M)); else the open-end form, rows reached to *h_rows
+void dtw_run(wm_engine* e, const float* d_x, int N, int M, int* h_i, int* h_j, int* h_len, hipStream_t st,
+             int* h_rows = nullptr) {
+  if (h_rows && (N <= 0 || M <= 0)) throw std::runtime_error("wm_dtw_open: bad matrix shape");
   e->a_cost.ensure((size_t)(N + 1) * (M + 1) * 4);
   e->a_trace.ensure((size_t)(N + 1) * (M + 1));
   e->a_pi.ensure((size_t)(N + M + 2) * 4);
   e->a_pj.ensure((size_t)(N + M + 2) * 4);
-  e->a_plen.ensure(4);
-  launch_dtw(d_x, N, M, e->a_cost.as<float>(), e->a_trace.as<signed char>(), e->a_pi.as<int>(), e->a_pj.as<int>(),
-             e->a_plen.as<int>(), st);
-  int n = 0;
-  HIP_OK(hipMemcpyAsync(&n, e->a_plen.p, 4, hipMemcpyDeviceToHost, st));
+  e->a_plen.ensure(8);                              // path length, rows reached
+  int nr[2] = {0, 0};
+  if (h_rows)
+    launch_dtw_open(d_x, N, M, e->a_cost.as<float>(), e->a_trace.as<signed char>(), e->a_pi.as<int>(),
+                    e->a_pj.as<int>(), e->a_plen.as<int>(), e->a_plen.as<int>() + 1, st);
+  else
+    launch_dtw(d_x, N, M, e->a_cost.as<float>(), e->a_trace.as<signed char>(), e->a_pi.as<int>(), e->a_pj.as<int>(),
+               e->a_plen.as<int>(), st);
+  HIP_OK(hipMemcpyAsync(nr, e->a_plen.p, h_rows ? 8 : 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
+  const int n = nr[0];
+  if (h_rows) {
+    if (nr[1] <= 0) throw std::runtime_error("wm_dtw_open: non-finite alignment cost (item 0)");
+    *h_rows = nr[1];
+  }
   HIP_OK(hipMemcpyAsync(h_i, e->a_pi.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipMemcpyAsync(h_j, e->a_pj.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
@@ -2139,20 +2154,24 @@ void align(wm_engine* e, int slot, int sot_len, const int* h_sot, int n_text, co
 // teacher-forced decoder pass over every item (sequences padded with <|endoftext|> to the chunk's longest: the
 // pass is causal, so padding never changes a real position), then per item the probabilities and the
 // alignment matrix, and one batched DTW launch for the whole chunk.
+// h_rows null: wm_align_batch (every path ends at its matrix' last row).  h_rows [n]: wm_align_open_batch, the same
+// pass, capture, probabilities and matrices with the open-end batched DTW; item i's rows reached go to h_rows[i],
+// and an item whose minimum end cost is not finite fails the call.
 void align_batch(wm_engine* e, int n, const int* h_slots, int sot_len, const int* h_sot, const int* h_text_off,
                  const int* h_text, const int* h_num_frames, const int* h_heads, int n_heads, int medw, float* h_probs,
-                 const long long* h_path_off, int* h_pi, int* h_pj, int* h_plen, hipStream_t st) {
+                 const long long* h_path_off, int* h_pi, int* h_pj, int* h_plen, hipStream_t st, int* h_rows = nullptr) {
   const auto& m = e->dm;
   const int T = m.n_audio_ctx, V = m.n_vocab;
+  const std::string who = h_rows ? "wm_align_open_batch" : "wm_align_batch";
   if (n <= 0) return;
-  if (n_heads <= 0) throw std::runtime_error("wm_align_batch: no alignment heads");
+  if (n_heads <= 0) throw std::runtime_error(who + ": no alignment heads");
   std::vector<int> S(n), nt(n), F(n);
   for (int i = 0; i < n; ++i) {
     nt[i] = h_text_off[i + 1] - h_text_off[i];
     S[i] = sot_len + 1 + nt[i] + 1;
     F[i] = h_num_frames[i] / 2;
-    if (nt[i] <= 0 || S[i] > m.n_text_ctx) throw std::runtime_error("wm_align_batch: bad token count");
-    if (F[i] <= 0 || F[i] > T) throw std::runtime_error("wm_align_batch: bad num_frames");
+    if (nt[i] <= 0 || S[i] > m.n_text_ctx) throw std::runtime_error(who + ": bad token count");
+    if (F[i] <= 0 || F[i] > T) throw std::runtime_error(who + ": bad num_frames");
   }
   // The capture buffer (S x heads x 1500 f32 per item: ~230 MB for a large-v3 window with the default 320 heads)
   // may take half of the free device memory (at most 48 GB): a batch of 150 large-v3 windows then aligns in ONE
@@ -2269,18 +2288,27 @@ void align_batch(wm_engine* e, int n, const int* h_slots, int sot_len, const int
     e->a_trace.ensure((size_t)ct);
     e->a_pi.ensure((size_t)pt * 4);
     e->a_pj.ensure((size_t)pt * 4);
-    e->a_plen.ensure((size_t)c * 4);
-    launch_dtw_batch(e->a_mat.as<float>(), d_xo, d_N, d_M, e->a_cost.as<float>(), e->a_trace.as<signed char>(), d_co,
-                     e->a_pi.as<int>(), e->a_pj.as<int>(), d_po, e->a_plen.as<int>(), c, st);
-    std::vector<int> pi(pt), pj(pt), plen(c);
+    e->a_plen.ensure((size_t)c * 8);                 // path lengths [c], then rows reached [c]
+    if (h_rows)
+      launch_dtw_open_batch(e->a_mat.as<float>(), d_xo, d_N, d_M, e->a_cost.as<float>(), e->a_trace.as<signed char>(),
+                            d_co, e->a_pi.as<int>(), e->a_pj.as<int>(), d_po, e->a_plen.as<int>(),
+                            e->a_plen.as<int>() + c, c, st);
+    else
+      launch_dtw_batch(e->a_mat.as<float>(), d_xo, d_N, d_M, e->a_cost.as<float>(), e->a_trace.as<signed char>(), d_co,
+                       e->a_pi.as<int>(), e->a_pj.as<int>(), d_po, e->a_plen.as<int>(), c, st);
+    std::vector<int> pi(pt), pj(pt), plen(h_rows ? 2 * c : c);
     std::vector<float> probs(ntext);                // in chunk order: item k's text tokens after item k-1's
     HIP_OK(hipMemcpyAsync(probs.data(), e->a_probs.p, ntext * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(pi.data(), e->a_pi.p, pt * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(pj.data(), e->a_pj.p, pt * 4, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(plen.data(), e->a_plen.p, c * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(plen.data(), e->a_plen.p, plen.size() * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     for (int k = 0, pos = 0; k < c; ++k) {
       const int i = ord[i0 + k];
+      if (h_rows) {
+        if (plen[c + k] <= 0) throw std::runtime_error(who + ": non-finite alignment cost (item " + std::to_string(i) + ")");
+        h_rows[i] = plen[c + k];
+      }
       for (int j = 0; j < nt[i]; ++j) h_probs[h_text_off[i] + j] = probs[pos + j];
       pos += nt[i];
       h_plen[i] = plen[k];
@@ -2856,6 +2884,30 @@ int wm_align_batch(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t sot_
 int wm_dtw(wm_engine* e, const float* d_cost, int32_t n, int32_t m, int32_t* h_text_idx, int32_t* h_time_idx,
            int32_t* h_path_len, void* stream) {
   return guarded(e, [&] { dtw_run(e, d_cost, n, m, h_text_idx, h_time_idx, h_path_len, (hipStream_t)stream); });
+}
+
+int wm_dtw_open(wm_engine* e, const float* d_cost, int32_t n, int32_t m, int32_t* h_text_idx, int32_t* h_time_idx,
+                int32_t* h_path_len, int32_t* h_rows, void* stream) {
+  return guarded(e, [&] {
+    if (!h_rows) throw std::runtime_error("wm_dtw_open: null h_rows");
+    dtw_run(e, d_cost, n, m, h_text_idx, h_time_idx, h_path_len, (hipStream_t)stream, h_rows);
+  });
+}
+
+int wm_align_open_batch(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t sot_len, const int32_t* h_sot,
+                        const int32_t* h_text_off, const int32_t* h_text, const int32_t* h_num_frames,
+                        const int32_t* h_heads, int32_t n_heads, int32_t median_filter_width, float* h_probs,
+                        const int64_t* h_path_off, int32_t* h_text_idx, int32_t* h_time_idx, int32_t* h_path_len,
+                        int32_t* h_rows, void* stream) {
+  return guarded(e, [&] {
+    require_weights(e);
+    check_weights(e);
+    if (!h_rows) throw std::runtime_error("wm_align_open_batch: null h_rows");
+    for (int i = 0; i < n; ++i)
+      if (h_slots[i] < 0 || h_slots[i] >= e->n_slots) throw std::runtime_error("wm_align_open_batch: slot out of range");
+    align_batch(e, n, h_slots, sot_len, h_sot, h_text_off, h_text, h_num_frames, h_heads, n_heads, median_filter_width,
+                h_probs, (const long long*)h_path_off, h_text_idx, h_time_idx, h_path_len, (hipStream_t)stream, h_rows);
+  });
 }
 
 int wm_encoder_attention(wm_engine* e, const void* d_qkv, void* d_out, int32_t B, int32_t T, void* stream) {

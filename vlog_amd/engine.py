@@ -480,6 +480,16 @@ class GpuEngine:
                     num_frames: Sequence[int], alignment_heads: Sequence[Tuple[int, int]], median_filter_width: int = 7):
         """wm_align_batch: CTranslate2 Whisper.align for several windows at once -> one (text_token_probs,
         text_indices, time_indices) per window (every window needs >= 1 text token)."""
+        return self._align_batch(False, slots, sot_sequence, texts, num_frames, alignment_heads, median_filter_width)
+
+    def align_open_batch(self, slots: Sequence[int], sot_sequence: Sequence[int], texts: Sequence[Sequence[int]],
+                         num_frames: Sequence[int], heads: Sequence[Tuple[int, int]], median_filter_width: int = 7):
+        """wm_align_open_batch: align_batch with the open-end DTW (forced alignment: a window's text may run past its
+        audio) -> one (text_token_probs, text_indices, time_indices, rows) per window.  rows = R, the smallest end row
+        in [1, n_text + 1] of minimum cost: the path visits rows 0 .. R-1; R == n_text + 1 is align_batch's path."""
+        return self._align_batch(True, slots, sot_sequence, texts, num_frames, heads, median_filter_width)
+
+    def _align_batch(self, open_end: bool, slots, sot_sequence, texts, num_frames, alignment_heads, median_filter_width):
         n = len(slots)
         if n == 0:
             return []
@@ -497,28 +507,41 @@ class GpuEngine:
         ti = np.zeros(sum(cap), dtype=np.int32)
         tj = np.zeros(sum(cap), dtype=np.int32)
         plen = np.zeros(n, dtype=np.int32)
+        rows = np.zeros(n, dtype=np.int32)
         hs = np.ascontiguousarray(slots, dtype=np.int32)
+        args = (self.h, n, _i32p(hs), len(sot), _i32p(sot), _i32p(off), _i32p(text), _i32p(nf), _i32p(heads), heads.shape[0],
+                median_filter_width, _f32p(probs), poff.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(ti), _i32p(tj),
+                _i32p(plen))
         with torch.cuda.device(self.device):
-            _capi.check(self.lib.wm_align_batch(self.h, n, _i32p(hs), len(sot), _i32p(sot), _i32p(off), _i32p(text), _i32p(nf),
-                                                _i32p(heads), heads.shape[0], median_filter_width, _f32p(probs),
-                                                poff.ctypes.data_as(C.POINTER(C.c_int64)), _i32p(ti), _i32p(tj),
-                                                _i32p(plen), self.stream_ptr()), "wm_align_batch")
+            if open_end:
+                _capi.check(self.lib.wm_align_open_batch(*args, _i32p(rows), self.stream_ptr()), "wm_align_open_batch")
+            else:
+                _capi.check(self.lib.wm_align_batch(*args, self.stream_ptr()), "wm_align_batch")
         out = []
         for i in range(n):
             a, k = int(poff[i]), int(plen[i])
-            out.append((probs[off[i]: off[i + 1]].copy(), ti[a: a + k].copy(), tj[a: a + k].copy()))
+            item = (probs[off[i]: off[i + 1]].copy(), ti[a: a + k].copy(), tj[a: a + k].copy())
+            out.append(item + (int(rows[i]),) if open_end else item)
         return out
 
-    def dtw(self, cost: torch.Tensor):
-        """DTW path of a device cost matrix [N, M] (f32)."""
+    def dtw(self, cost: torch.Tensor, open_end: bool = False):
+        """DTW path of a device cost matrix [N, M] (f32) -> (text_indices, time_indices).  open_end=True: the open-end
+        form (wm_dtw_open: the path ends at the smallest row R of minimum cost in the last column) ->
+        (text_indices, time_indices, R); a matrix whose minimum end cost is not finite raises RuntimeError."""
         cost = cost.to(self.device, torch.float32).contiguous()
         N, M = cost.shape
         ti = np.zeros(N + M + 2, dtype=np.int32)
         tj = np.zeros(N + M + 2, dtype=np.int32)
         n = np.zeros(1, dtype=np.int32)
+        rows = np.zeros(1, dtype=np.int32)
         with torch.cuda.device(self.device):
-            _capi.check(self.lib.wm_dtw(self.h, C.c_void_p(cost.data_ptr()), N, M, _i32p(ti), _i32p(tj), _i32p(n),
-                                        self.stream_ptr()), "wm_dtw")
+            if open_end:
+                _capi.check(self.lib.wm_dtw_open(self.h, C.c_void_p(cost.data_ptr()), N, M, _i32p(ti), _i32p(tj), _i32p(n),
+                                                 _i32p(rows), self.stream_ptr()), "wm_dtw_open")
+            else:
+                _capi.check(self.lib.wm_dtw(self.h, C.c_void_p(cost.data_ptr()), N, M, _i32p(ti), _i32p(tj), _i32p(n),
+                                            self.stream_ptr()), "wm_dtw")
         k = int(n[0])
+        if open_end:
+            return ti[:k].copy(), tj[:k].copy(), int(rows[0])
         return ti[:k].copy(), tj[:k].copy()
-

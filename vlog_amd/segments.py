@@ -8,11 +8,15 @@
   compression_ratio — len(utf8) / len(zlib(utf8)) (fallback trigger above 2.4).
   needs_fallback — the generate_with_fallback decision (compression ratio, avg logprob, silence exemption).
   avg_logprob — recovered from the CTranslate2 score: score * len**length_penalty / (len + 1).
+  _word_means, merge_punctuations — the word tail of `find_alignment` / `add_word_timestamps`, shared by the word
+      timestamps (transcribe.py) and the forced alignment (forced_align.py).
 """
 from __future__ import annotations
 
 import zlib
 from typing import Callable, List, Optional, Sequence, Tuple
+
+import numpy as np
 
 TIME_PRECISION = 0.02
 INPUT_STRIDE = 2
@@ -122,3 +126,43 @@ def should_skip_window(no_speech_prob: float, avg_lp: float, no_speech_threshold
     if log_prob_threshold is not None and avg_lp > log_prob_threshold:
         skip = False
     return skip
+
+
+def _word_means(probs: np.ndarray, wb: np.ndarray) -> List[float]:
+    """[float(np.mean(probs[i:j])) ...] over consecutive word boundaries, with np.mean's own arithmetic spelled out for
+    float32 (np.add.reduce of the slice, divided by the count in float64, rounded to float32): the same values
+    without np.mean's per-call overhead (half the host time of config 5's word probabilities)."""
+    p = np.asarray(probs)
+    b = np.asarray(wb).tolist()
+    if p.dtype != np.float32:
+        return [float(np.mean(p[i:j])) for i, j in zip(b[:-1], b[1:])]
+    add = np.add.reduce
+    return [float(np.float32(float(add(p[i:j])) / (j - i))) if j > i else float(np.mean(p[i:j]))
+            for i, j in zip(b[:-1], b[1:])]
+
+
+def merge_punctuations(alignment: List[dict], prepended: str, appended: str) -> None:
+    """faster-whisper / openai merge_punctuations."""
+    i = len(alignment) - 2
+    j = len(alignment) - 1
+    while i >= 0:
+        prev, foll = alignment[i], alignment[j]
+        if prev["word"].startswith(" ") and prev["word"].strip() in prepended:
+            foll["word"] = prev["word"] + foll["word"]
+            foll["tokens"] = prev["tokens"] + foll["tokens"]
+            prev["word"] = ""
+            prev["tokens"] = []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(alignment):
+        prev, foll = alignment[i], alignment[j]
+        if not prev["word"].endswith(" ") and foll["word"] in appended:
+            prev["word"] = prev["word"] + foll["word"]
+            prev["tokens"] = prev["tokens"] + foll["tokens"]
+            foll["word"] = ""
+            foll["tokens"] = []
+        else:
+            i = j
+        j += 1

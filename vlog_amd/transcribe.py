@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import segments as segs
+from .segments import _word_means, merge_punctuations
 from .audio import mono_f32, read_wav
 from .seek_state import (ENERGY_FRAME_MEL, MAX_SECTIONS, SeekState, chunk_joins, decode_round_with, fallback_ladder,
                          iter_lockstep, plan_sections, run_lockstep, window_max_length)
@@ -128,6 +129,19 @@ class TranscriptionInfo:
     all_language_probs: Optional[List[Tuple[str, float]]]
     transcription_options: TranscriptionOptions
     vad_options: Optional[VadOptions]
+
+
+@dataclass
+class AlignmentInfo:
+    """What WhisperModel.align reports beside its segments.  window_rows: per window (seek in mel frames, rows
+    offered = candidate tokens + 1, rows the open-end DTW reached)."""
+    language: str
+    language_probability: float
+    duration: float
+    duration_after_vad: float
+    windows: int
+    unaligned_words: int
+    window_rows: List[Tuple[int, int, int]]
 
 
 @dataclass
@@ -741,6 +755,65 @@ class WhisperModel:
             out.append((segments, info))
         return out
 
+    # ------------------------------------------------------------------ forced alignment
+    def align(self, audio: Union[str, BinaryIO, np.ndarray], text: Union[str, Sequence[str]],
+              language: Optional[str] = None, task: str = "transcribe", vad_filter: bool = False, vad_parameters=None,
+              max_window_tokens: int = 224, max_cue_chars: Optional[int] = 84, median_filter_width: int = 7,
+              prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、"
+              ) -> Tuple[List[Segment], AlignmentInfo]:
+        """Forced alignment: time a GIVEN transcript against the audio (re-timing an edited transcript; nothing is
+        decoded).  text: a str (one caption line per "\n") or a sequence of lines.  -> (segments, AlignmentInfo):
+        one Segment per line, or its cues when the line is longer than max_cue_chars (None: never cut), each with
+        its Words; ids 1, 2, ...; temperature and no_speech_prob 0.0; avg_logprob the mean log-probability the
+        model gives the line's tokens.
+
+        The loop (vlog_amd/forced_align.py): every 30 s window is offered the next max_window_tokens tokens of
+        whole words, runs the teacher-forced pass with the alignment heads captured, and the open-end DTW
+        (wm_align_open_batch) returns the path and how many text rows the window's audio reached; the words whose
+        end was reached are timed and the next window starts at the last of them.  Words left when the audio ends get
+        start = end = duration and probability 0.0 (info.unaligned_words).  vad_filter=True runs the loop on the
+        collected speech and maps the times back (a silent window gives the DTW nothing to hold on to).
+        Audio loading, resampling, log-mel and language detection are transcribe's; the whole call holds the
+        model lock.  Raises ValueError in throughput mode and for an empty text."""
+        from . import forced_align as fa
+        if self.throughput:
+            raise ValueError("align is the sequential mode's; throughput mode has no forced alignment")
+        if task not in ("transcribe", "translate"):
+            raise ValueError(f"unknown task {task!r}")
+        if not fa.split_lines(text):
+            raise ValueError("align: empty text")
+        with self._lock:
+            features, tokenizer, options, tinfo, speech_chunks = self._prepare_file(
+                audio, language=language, task=task, beam_size=1, best_of=1, patience=1, length_penalty=1,
+                repetition_penalty=1, no_repeat_ngram_size=0, temperature=0.0, compression_ratio_threshold=None,
+                log_prob_threshold=None, no_speech_threshold=None, condition_on_previous_text=False,
+                prompt_reset_on_temperature=0.5, initial_prompt=None, prefix=None, suppress_blank=True,
+                suppress_tokens=[-1], without_timestamps=True, max_initial_timestamp=1.0, word_timestamps=True,
+                prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations, multilingual=False,
+                vad_filter=vad_filter, vad_parameters=vad_parameters, max_new_tokens=None, clip_timestamps="0",
+                hallucination_silence_threshold=None, hotwords=None, language_detection_threshold=0.5,
+                language_detection_segments=1)
+            heads = self.dims.default_alignment_heads()
+            self._use_cross_form(1)             # one teacher-forced row set per window, as a greedy decode's alignment
+
+            def align_window(seek: int, size: int, tokens: List[int]):
+                self._encode(features, seek, size, 0)
+                return self.engine.align_open_batch([0], tokenizer.sot_sequence, [tokens], [size], heads,
+                                                    median_filter_width)[0]
+
+            out, stats = fa.forced_align(tokenizer, text, features.shape[1] - 1, tinfo.duration_after_vad, align_window,
+                                         max_window_tokens, max_cue_chars, prepend_punctuations, append_punctuations,
+                                         self.frames_per_second, self.tokens_per_second)
+        segments = [self._segment(d) for d in out]
+        if speech_chunks:
+            from .vad import restore_speech_timestamps
+            segments = list(restore_speech_timestamps(iter(segments), speech_chunks, SAMPLE_RATE))
+        info = AlignmentInfo(language=tinfo.language, language_probability=tinfo.language_probability,
+                             duration=tinfo.duration, duration_after_vad=tinfo.duration_after_vad,
+                             windows=stats["windows"], unaligned_words=stats["unaligned_words"],
+                             window_rows=stats["window_rows"])
+        return segments, info
+
     # ------------------------------------------------------------------ word timestamps
     def find_alignment(self, tokenizer: Tokenizer, text_tokens: List[List[int]], num_frames: Union[int, Sequence[int]],
                        median_filter_width: int = 7, slots: Optional[Sequence[int]] = None) -> List[List[dict]]:
@@ -842,46 +915,6 @@ class WhisperModel:
                     last_speech_timestamp = sub["end"]
                 segments[si][ssi]["words"] = words
         return last_speech_timestamp
-
-
-def _word_means(probs: np.ndarray, wb: np.ndarray) -> List[float]:
-    """[float(np.mean(probs[i:j])) ...] over consecutive word boundaries, with np.mean's own arithmetic spelled out for
-    float32 (np.add.reduce of the slice, divided by the count in float64, rounded to float32): the same values
-    without np.mean's per-call overhead (half the host time of config 5's word probabilities)."""
-    p = np.asarray(probs)
-    b = np.asarray(wb).tolist()
-    if p.dtype != np.float32:
-        return [float(np.mean(p[i:j])) for i, j in zip(b[:-1], b[1:])]
-    add = np.add.reduce
-    return [float(np.float32(float(add(p[i:j])) / (j - i))) if j > i else float(np.mean(p[i:j]))
-            for i, j in zip(b[:-1], b[1:])]
-
-
-def merge_punctuations(alignment: List[dict], prepended: str, appended: str) -> None:
-    """faster-whisper / openai merge_punctuations."""
-    i = len(alignment) - 2
-    j = len(alignment) - 1
-    while i >= 0:
-        prev, foll = alignment[i], alignment[j]
-        if prev["word"].startswith(" ") and prev["word"].strip() in prepended:
-            foll["word"] = prev["word"] + foll["word"]
-            foll["tokens"] = prev["tokens"] + foll["tokens"]
-            prev["word"] = ""
-            prev["tokens"] = []
-        else:
-            j = i
-        i -= 1
-    i, j = 0, 1
-    while j < len(alignment):
-        prev, foll = alignment[i], alignment[j]
-        if not prev["word"].endswith(" ") and foll["word"] in appended:
-            prev["word"] = prev["word"] + foll["word"]
-            prev["tokens"] = prev["tokens"] + foll["tokens"]
-            foll["word"] = ""
-            foll["tokens"] = []
-        else:
-            i = j
-        j += 1
 
 
 @dataclass
