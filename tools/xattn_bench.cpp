@@ -7,11 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "../vlog_amd/csrc/common.h"
-void launch_xattn(const bf16*, const void*, const float*, const int*, const int*, const int*, int, long long, int, int,
-                  int, int, int, int, int, bf16*, float*, float*, const int*, int, unsigned long long*, hipStream_t,
-                  hipEvent_t, hipEvent_t);
-void xattn_set_ablation(int);
+#include "../vlog_amd/csrc/attn.h"
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
 int main(int argc, char** argv) {

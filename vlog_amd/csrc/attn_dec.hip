@@ -11,7 +11,7 @@
 // (max, sum, o) partials.  8 lanes cover one 128-B key row (16 B per lane), 8 keys per wave-instruction:
 // fully coalesced 1 KiB per wave load.  Finished hypotheses are skipped (their rows still flow through
 // the weight-bound GEMMs, which read the weights once per step regardless).
-#include "common.h"
+#include "attn.h"
 #include <type_traits>
 #include <hip/hip_ext.h>
 #include <algorithm>
@@ -287,6 +287,9 @@ __device__ __forceinline__ void cross_item(const DecAttnArgs& a, int bx, int spl
     any |= live[r];
   }
   if (!any) return;
+  // No split is empty: a trailing split has nk <= 0 only if (splits - 1) ceil(T / splits) >= T, which needs
+  // (splits - 1)^2 >= T, and launch_cross_attn keeps splits <= min(16, ceil(T / 128)), i.e. T > 128 (splits - 1) >=
+  // (splits - 1)^2 (at T = 1500: at most 12 splits of 125 keys).  dec_attn_kernel<false> runs with one split only.
   const int chunk = (a.T + a.splits - 1) / a.splits;
   const int k0 = split * chunk;
   const int nk = min(a.T, k0 + chunk) - k0;
@@ -437,8 +440,9 @@ __device__ __forceinline__ void cross_item(const DecAttnArgs& a, int bx, int spl
       O += s_o[w][r][e] * c;
     }
     const int row = row0 + r;
+    if (a.done && a.done[a.row_hyp[row]]) continue;      // a finished row: neither output nor partial
     if (a.splits == 1) {
-      if (!(a.done && a.done[a.row_hyp[row]])) a.out[(long long)row * a.ldo + h * HD + e] = f2bf(O / L);
+      a.out[(long long)row * a.ldo + h * HD + e] = f2bf(O / L);
     } else if (a.cnt) {
       // hand-off to the last-arriving split: write-through (sc1) stores of the partial, drained, then one
       // agent-scope ticket per item (cdna_hip_programming.md §6 Guideline 16, R1 / counter form)
@@ -683,7 +687,16 @@ __global__ __launch_bounds__(256) void cross_capture_kernel(DecAttnArgs a, int g
   const int g = rb / bpg, j = rb - g * bpg;
   const int r0 = g * group + j * RG, nr = min(RG, group - j * RG);
   const int hyp0 = a.row_hyp[r0];
-  if (a.done && a.done[hyp0]) return;
+  // liveness per ROW (the group kernel's rule): the block runs while any of its rows is live and writes the output and
+  // the probabilities of live rows only
+  bool live[RG];
+  bool any = false;
+#pragma unroll
+  for (int r = 0; r < RG; ++r) {
+    live[r] = r < nr && !(a.done && a.done[a.row_hyp[r0 + min(r, nr - 1)]]);
+    any |= live[r];
+  }
+  if (!any) return;
   const long long off = ((long long)a.hyp_slot[hyp0] * H + h) * ((long long)T * HD);
   const bf16* K = a.kbase + off;
   const bf16* V = a.vbase + off;
@@ -738,7 +751,9 @@ __global__ __launch_bounds__(256) void cross_capture_kernel(DecAttnArgs a, int g
   __syncthreads();
   if (a.probs && a.head_map[h] >= 0) {
     const int hm = a.head_map[h];
-    for (int r = 0; r < nr; ++r) {
+#pragma unroll
+    for (int r = 0; r < RG; ++r) {
+      if (!live[r]) continue;
       const float inv = 1.0f / s_sum[r];
       float* pr = a.probs + ((long long)(r0 + r) * a.n_align + hm) * T;
       for (int p = tid; p < T; p += 256) pr[p] = s_sc[r][p] * inv;
@@ -781,6 +796,7 @@ __global__ __launch_bounds__(256) void cross_capture_kernel(DecAttnArgs a, int g
   for (int idx = tid; idx < nr * HD; idx += 256) {
     const int r = idx / HD, e = idx - r * HD;
     const float v = s_acc[0][r][e] + s_acc[1][r][e] + s_acc[2][r][e] + s_acc[3][r][e];
+    if (a.done && a.done[a.row_hyp[r0 + r]]) continue;
     a.out[(long long)(r0 + r) * a.ldo + h * HD + e] = f2bf(v / s_sum[r]);
   }
 }
@@ -799,7 +815,6 @@ __global__ __launch_bounds__(256) void cross_capture_kernel(DecAttnArgs a, int g
 typedef __attribute__((ext_vector_type(4))) short tf_i16x4;
 typedef __attribute__((ext_vector_type(2))) int tf_i32x2;
 #define TF_KT 64
-#define TF_THR 8.0f
 __device__ __forceinline__ int tf_kslot(int r, int c) { return r * 64 + ((c ^ ((r >> 1) & 7)) << 3); }
 __device__ __forceinline__ int tf_vslot(int r, int c) { return r * 64 + ((c ^ (((r >> 1) & 1) << 2)) << 3); }
 
@@ -982,7 +997,8 @@ __global__ __launch_bounds__(256, 2) void cross_tf_kernel(DecAttnArgs a, int gro
     m_run = M;
   }
   const float inv_cap = cap ? 1.0f / l_run : 0.f;
-  float* prow = cap && valid ? a.probs + ((long long)(row0 + r) * a.n_align + hm) * T : nullptr;
+  // (live rows only, as the output: a finished row's probabilities are not written)
+  float* prow = cap && live ? a.probs + ((long long)(row0 + r) * a.n_align + hm) * T : nullptr;
 
   f32x16 o[2];
 #pragma unroll
@@ -1007,7 +1023,7 @@ __global__ __launch_bounds__(256, 2) void cross_tf_kernel(DecAttnArgs a, int gro
 #pragma unroll
         for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sc[kb][e]);
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      if (__any(mx > m_run + TF_THR)) {
+      if (__any(mx > m_run + CROSS_TF_RESCALE_THR)) {
         const float mn = fmaxf(m_run, mx);
         const float alpha = exp2f(m_run - mn);
         l_run *= alpha;
@@ -1066,7 +1082,7 @@ __global__ __launch_bounds__(256, 2) void cross_tf_kernel(DecAttnArgs a, int gro
     // the combine folded in: every split writes its partial through to L2 (agent-scope stores), drains, and takes
     // one ticket per (group, head, row tile); the last arriver combines with cross_combine_kernel's arithmetic and
     // order (bit-identical to the separate kernel) and re-arms the counter (cdna_hip_programming.md §6 Guideline 16)
-    if (valid) {
+    if (live) {                          // (a finished row leaves no partial)
       const long long pi = ((long long)(row0 + r) * H + h) * a.splits + sp;
 #pragma unroll
       for (int hb = 0; hb < 2; ++hb)
@@ -1103,7 +1119,8 @@ __global__ __launch_bounds__(256, 2) void cross_tf_kernel(DecAttnArgs a, int gro
     }
     return;
   }
-  if (valid && a.splits > 1) {
+  if (a.splits > 1) {
+    if (!live) return;                   // (a finished row leaves no partial; the combine drops its row unread)
     // partial of this key split (unnormalised o, its max and sum in log2 units) for cross_combine_kernel
     const long long pi = ((long long)(row0 + r) * H + h) * a.splits + sp;
 #pragma unroll

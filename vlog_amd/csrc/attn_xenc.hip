@@ -35,7 +35,7 @@
 //   xcomb_vo_kernel merges the key splits (weights l_s 2^(m_s - M) / L) and applies Wv_h and bv_h (MFMA,
 //                   K = d) -> the attention output ao [rows][d].  With capture on, it also turns the raw
 //                   scores that xattn wrote for the alignment heads into probabilities.
-#include "common.h"
+#include "attn.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <cstdlib>
@@ -43,7 +43,6 @@
 #include <string>
 #include <type_traits>
 
-#define XTHR 8.0f              // deferred-rescale threshold (log2 units)
 #define XMAXS 16               // max key splits
 
 typedef __attribute__((ext_vector_type(4))) short xi16x4;
@@ -426,7 +425,7 @@ __device__ __forceinline__ void xattn_segment(const XAttnArgs& a, char* smem, in
 #pragma unroll
     for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[r]);
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    if (__any(mx > m_run + XTHR)) {
+    if (__any(mx > m_run + XATTN_RESCALE_THR)) {
       const float mn = fmaxf(m_run, mx);
       const float alpha = __builtin_amdgcn_exp2f(m_run - mn);
       l_run *= alpha;
@@ -645,12 +644,14 @@ __global__ __launch_bounds__(512) void xcomb_vo_kernel(XCombArgs a) {
   if (a.probs) {
     const int hm = a.head_map[h];
     if (hm >= 0) {
-      for (int idx = tid; idx < RT * a.T; idx += 512) {
-        const int ri = idx / a.T, t = idx - ri * a.T;
+      // row by row (uniform): a finished row holds no scores from xattn and is left as it is, like its output
+      for (int ri = 0; ri < RT; ++ri) {
         const int rr = bx * RT + ri;
-        if (rr >= a.rows) continue;
-        float* p = a.probs + ((long long)rr * a.n_align + hm) * a.T + t;
-        *p = __builtin_amdgcn_exp2f(*p - sML[ri][0]) / sML[ri][1];
+        if (rr >= a.rows) break;
+        if (a.done && a.done[a.row_hyp[rr]]) continue;
+        float* pb = a.probs + ((long long)rr * a.n_align + hm) * a.T;
+        const float Mr = sML[ri][0], Lr = sML[ri][1];
+        for (int t = tid; t < a.T; t += 512) pb[t] = __builtin_amdgcn_exp2f(pb[t] - Mr) / Lr;
       }
     }
   }
@@ -771,6 +772,10 @@ void launch_xq(const bf16* q, long long ldq, const CrossFuse& fz, const bf16* wk
                hipStream_t st) {
   if (rows <= 0) return;
   if (d != H * 64) throw std::runtime_error("xq: n_state must be n_head * 64");
+  {
+    int qw = 0, nw = 0;
+    xattn_geometry(d, qw, nw);             // (throws: only the n_state values the attention kernel is built for)
+  }
   if (fz.q_part && fz.q_splits > XMAXS) throw std::runtime_error("xq: too many cq split-K slabs");
   XQArgs a{};
   a.q = q; a.ldq = ldq; a.q_part = fz.q_part; a.q_splits = fz.q_splits; a.q_rows = fz.q_rows; a.q_bias = fz.q_bias;

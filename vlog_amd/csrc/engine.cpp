@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/whisper_mi355.h"
+#include "attn.h"
 #include "gemm.h"
 #include "search.h"
 #include "vad.h"
@@ -39,23 +40,7 @@ void launch_embed(const int*, const int*, const bf16*, const float*, float*, int
 void launch_im2col_conv1(const float*, long long, const int*, const int*, int, int, int, bf16*, hipStream_t);
 void launch_zero_pad_rows(bf16*, int, long long, int, hipStream_t);
 void launch_attn_enc(const bf16*, bf16*, int, int, int, int, hipStream_t);
-void launch_self_attn(const bf16*, long long, const bf16*, const bf16*, const int*, const int*, const int*, const int*,
-                      bf16*, long long, int, int, int, unsigned long long*, hipStream_t, hipEvent_t, hipEvent_t, int, int);
-void launch_cross_attn(const bf16*, long long, const bf16*, const bf16*, int, const int*, const int*, const int*, bf16*,
-                       long long, int, int, int, float*, float*, float*, float*, const int*, int, int, int,
-                       const CrossFuse&, unsigned long long*, hipStream_t, hipEvent_t, hipEvent_t);
-
-// factored cross-attention over the encoder output (attn_xenc.hip)
-void launch_xpack(const bf16*, bf16*, bf16*, int, int, int, hipStream_t);
-void launch_xq(const bf16*, long long, const CrossFuse&, const bf16*, bf16*, int, int, int, hipStream_t);
-int xattn_splits(int, int, int, int, int);
-void launch_xquant8(const bf16*, long long, int, unsigned char*, float*, hipStream_t);
-long long xblock_slot_elems(int T, int d);
-void launch_xblock(const bf16* src, int B, int T, int d, bf16* dst, bool to_blocked, hipStream_t st);
-void launch_xattn(const bf16*, const void*, const float*, const int*, const int*, const int*, int, long long, int, int, int, int,
-                  int, int, int, bf16*, float*, float*, const int*, int, unsigned long long*, hipStream_t, hipEvent_t, hipEvent_t);
-void launch_xcomb_vo(const bf16*, const float*, int, long long, const bf16*, const float*, const int*, const int*,
-                     bf16*, long long, int, int, int, int, float*, const int*, int, hipStream_t);
+// (the decoder attention launchers of attn_dec.hip / attn_xenc.hip: attn.h)
 
 void launch_token_probs(const float*, int, int, int, const int*, float*, hipStream_t);
 void launch_align_matrix(const float*, int, int, int, int, int, int, int, float*, float*, float*, hipStream_t);
