@@ -99,6 +99,22 @@ int wm_frame_energy(wm_engine* e, const float* d_pcm, int64_t n_samples, int32_t
  * (an all-zero row: zeros, scale 0).  wm_cross_kv applies it to the window slots when cross_fp8 is on. */
 int wm_cross_fp8_quantize(wm_engine* e, const void* d_enc, int64_t rows, uint8_t* d_codes, float* d_scale, void* stream);
 
+/* The quantisation of the projected form's fp8 K/V panels (wm_set_option "cross_kv_fp8"), exposed for tests.  A row is
+ * 64 bf16 values: the head_dim values of one (layer, K or V, slot, head, position) as the bf16 panels store them.
+ * Per row: 64 OCP e4m3 codes (d_codes [n_rows][64]) and one exponent byte b = e + 127 (d_exp [n_rows]); the stored
+ * value is e4m3(code) * 2^e.
+ *   - a row with a non-finite value: every code 0x7F (e4m3 NaN), b = 127;
+ *   - amax = max |x| == 0: every code 0x00, b = 127;
+ *   - otherwise e is the smallest integer with amax * 2^-e <= 448, from the bits of amax = m * 2^k (1 <= m < 2;
+ *     448 = 1.75 * 2^8): e = k - 8 if m <= 1.75, else k - 7, clamped to [-110, 110];
+ *   - code = round-to-nearest-even of x * 2^-e onto the e4m3 grid, saturating at +-448 (reachable only behind the
+ *     upper clamp of e).
+ * A dequantised value has at most 4 significant bits and is a normal number, so it is exactly a bf16 value: the fp8
+ * attention kernels compute on exactly the values a bf16 panel of the dequantised rows would hold.
+ * (Added without an ABI bump: a new entry point only.) */
+int wm_cross_kv_fp8_quantize(wm_engine* e, const void* d_rows_bf16, int64_t n_rows, uint8_t* d_codes, uint8_t* d_exp,
+                             void* stream);
+
 /* Silero VAD v5 (16 kHz) network weights, f32 device pointers in PyTorch layouts: STFT basis [258][256],
  * encoder convs conv_w[i] [out][in][3] with (in, out) = (129,128), (128,64), (64,64), (64,128) and biases
  * [out], LSTMCell w_ih/w_hh [512][128] (gate order i, f, g, o) and b_ih/b_hh [512], head conv1x1 [128] + [1]. */
@@ -135,7 +151,8 @@ int wm_reserve(wm_engine* e, int32_t n_slots, int32_t n_hyp, void* stream);
 /* Makes B encoder outputs the cross-attention memory of slots [slot0, slot0+B) (CTranslate2 projects them
  * to K/V inside generate [FW↑]).  Default (factored cross-attention): the slot keeps the encoder output
  * itself and the decoder attends over it (q' = Wk_h^T q, u = P E, Wv after the merge).  cross_mode 0: the
- * K/V projection of all decoder layers is computed here. */
+ * K/V projection of all decoder layers is computed here (with cross_kv_fp8 on, chunk by chunk through the
+ * quantiser: see the option). */
 int wm_cross_kv(wm_engine* e, const void* d_enc, int32_t B, int32_t slot0, void* stream);
 
 /* ctranslate2 Whisper.generate(encoder_output, prompts, ...) [FW↑] as faster-whisper
@@ -373,6 +390,16 @@ int wm_profile(wm_engine* e, int32_t enable);
  *   "encode_chunk" (default 160): windows per encoder pass inside wm_encode (~52 MB of activation scratch
  *   per large-v3 window).
  *   "cross_fp8" (default 0): opt-in fp8 (OCP e4m3) cross memory in the factored form (changes numerics).
+ *   "cross_kv_fp8" (default 0; VLOG_AMD_CROSS_KV_FP8): opt-in fp8 K/V panels of the PROJECTED form (cross_mode 0),
+ *   independent of cross_fp8: each knob governs its own form.  0 = bf16 panels (the same allocations and kernels as
+ *   without the option).  1 = e4m3 codes plus one exponent byte per 64-value row (the format of
+ *   wm_cross_kv_fp8_quantize): the slots take (64 + 1) / 128 of the bf16 bytes and every kernel that reads projected
+ *   panels converts a code to its exact bf16 value on load (changes numerics against 0).  2 = reference form for
+ *   tests and A/B: the same quantiser, the panels stored dequantised as bf16 and read by the bf16 kernels; 1 and 2
+ *   hold the same values.  In 1 and 2 wm_cross_kv projects 2 windows at a time into a bf16 staging buffer (2 x
+ *   245.8 MB = 491.5 MB at large-v3; a call with one window stages one, 245.8 MB) and quantises them into their
+ *   slots.  wm_destroy frees the staging and the exponent bytes with the slots.  Any other value is rejected.  Switching
+ *   re-allocates the window slots like cross_mode (their content is dropped: call wm_cross_kv again).
  *   "cross_tf" (default 1): the teacher-forced passes of wm_align / wm_align_batch (projected form) run the
  *   cross-attention on the matrix cores (bf16 MFMA, f32 scores and captured probabilities; the attention weights
  *   enter the V product as bf16); 0 = the f32 VALU kernels of the decode path.

@@ -21,6 +21,7 @@ SYMBOLS = (
     "wm_profile_read", "wm_set_option", "wm_get_option", "wm_encoder_attention",
     "wm_resample_plan", "wm_resample_taps", "wm_resample",
     "wm_dtw_open", "wm_align_open_batch",
+    "wm_cross_kv_fp8_quantize",
 )
 
 
@@ -88,6 +89,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "wm_resample_taps": (C.c_int, [i32, C.POINTER(C.c_float)]),
         "wm_resample": (C.c_int, [vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i64, vp, vp]),
         "wm_cross_fp8_quantize": (C.c_int, [vp, vp, i64, vp, vp, vp]),
+        "wm_cross_kv_fp8_quantize": (C.c_int, [vp, vp, i64, vp, vp, vp]),
         "wm_align": (C.c_int, [vp, i32, i32, C.POINTER(i32), i32, C.POINTER(i32), i32, C.POINTER(i32), i32, i32,
                                C.POINTER(C.c_float), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]),
         "wm_align_batch": (C.c_int, [vp, i32, C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),

@@ -21,6 +21,18 @@ void launch_cross_attn(const bf16* q, long long ldq, const bf16* kbase, const bf
                        float* part_m, float* part_l, float* part_o, float* probs, const int* head_map, int n_align,
                        int plan_rows, int cap, const CrossFuse& fz, unsigned long long* stat, hipStream_t st,
                        hipEvent_t ev0, hipEvent_t ev1);
+// The same operation on fp8 panels (common.h CrossKv8): same routing and split rules, the kernels' F8 instantiations,
+// which convert a code to its exact bf16 value on load.  A slot table is required.
+void launch_cross_attn_fp8(const bf16* q, long long ldq, const CrossKv8& kv, int T, const int* hyp_slot,
+                           const int* row_hyp, const int* done, bf16* out, long long ldo, int rows, int H, int group,
+                           float* part_m, float* part_l, float* part_o, float* probs, const int* head_map, int n_align,
+                           int plan_rows, int cap, const CrossFuse& fz, unsigned long long* stat, hipStream_t st,
+                           hipEvent_t ev0, hipEvent_t ev1);
+// Quantiser of those panels: rows of 64 bf16 -> 64 codes + 1 exponent byte (deq == nullptr), or the dequantised bf16
+// rows (deq != nullptr: the reference form).  Source row r goes to destination row
+// (r / src_per) * dst_stride + dst_off + r % src_per.
+void launch_kv8_quant(const bf16* src, long long n_rows, long long src_per, long long dst_stride, long long dst_off,
+                      unsigned char* codes, unsigned char* exps, bf16* deq, hipStream_t st);
 
 // ---- attn_xenc.hip: factored cross-attention over the encoder output
 void launch_xpack(const bf16* ckv_w, bf16* wkt, bf16* wvb, int L, int H, int d, hipStream_t st);

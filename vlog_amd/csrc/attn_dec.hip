@@ -33,6 +33,46 @@ __device__ __forceinline__ bf16x8 ld_stream(const bf16* p) {
   return __builtin_bit_cast(bf16x8, __builtin_nontemporal_load((const i32x4*)p));
 }
 
+// ---- fp8 cross K/V panels (engine option cross_kv_fp8, projected form).  A quantisation row is the 64 values of one
+// (layer, K|V, slot, head, position): 64 OCP e4m3 codes and one exponent byte b = e + 127, value = e4m3(code) * 2^e
+// (include/whisper_mi355.h wm_cross_kv_fp8_quantize has the definition).  A dequantised value has at most 4
+// significant bits and e stays in [-110, 110], so it is a normal bf16 number: the conversion below (hardware e4m3 ->
+// f32, an exact f32 product with 2^e, the upper 16 bits) is exact, and a kernel that converts on load computes on
+// exactly the bf16 values that a bf16 panel of the dequantised values would hold.  (gfx950 also has
+// v_cvt_scalef32_pk_bf16_fp8; this form is exact by construction and costs two VALU operations per value.)
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) int i32x2;
+__device__ __forceinline__ float kv8_scale(unsigned b) { return __uint_as_float(b << 23); }
+// one word of 4 codes -> 4 f32 values
+__device__ __forceinline__ void kv8_f32x4(int w, float sc, float* f) {
+  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+  f[0] = lo[0] * sc;
+  f[1] = lo[1] * sc;
+  f[2] = hi[0] * sc;
+  f[3] = hi[1] * sc;
+}
+// 8 codes -> 8 bf16 (the upper halves of the f32 products: exact, see above)
+__device__ __forceinline__ i32x4 kv8_bf16x8(i32x2 c, float sc) {
+  float f[8];
+  kv8_f32x4(c[0], sc, f);
+  kv8_f32x4(c[1], sc, f + 4);
+  i32x4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    r[i] = (int)__builtin_amdgcn_perm(__float_as_uint(f[2 * i + 1]), __float_as_uint(f[2 * i]), 0x07060302u);
+  return r;
+}
+__device__ __forceinline__ i32x2 ld_stream8(const unsigned char* p) {
+  return __builtin_nontemporal_load((const i32x2*)p);
+}
+// 8 codes at p with exponent byte b -> 8 f32 (the VALU kernels' load8 on an fp8 panel)
+__device__ __forceinline__ void kv8_load8(const unsigned char* p, unsigned b, float* f) {
+  const i32x2 c = *(const i32x2*)p;
+  const float sc = kv8_scale(b);
+  kv8_f32x4(c[0], sc, f);
+  kv8_f32x4(c[1], sc, f + 4);
+}
+
 struct DecAttnArgs {
   const bf16* q; long long ldq;
   const bf16* kbase; const bf16* vbase;   // cross: [slot][H][T][64] panels; self: [n_hyp][H][n_ctx][64]
@@ -53,6 +93,9 @@ struct DecAttnArgs {
   // head, hypothesis) in XCD-contiguous block order, so one head's waves of a window's beams run together on one XCD
   // and the history rows the beams share (the lineage) are fetched from HBM once and served by its L1 / L2
   int sgroup;
+  // cross, fp8 panels (the F8 instantiations; kbase / vbase are unused there): codes [slot][H][T][64] bytes and
+  // exponent bytes [slot][H][T] of this layer's K and V
+  const unsigned char* k8; const unsigned char* v8; const unsigned char* kexp; const unsigned char* vexp;
 };
 
 #define CT_MAX 1536
@@ -61,8 +104,10 @@ struct DecAttnArgs {
 // One 256-thread workgroup per (row, head[, key split]); 4 waves x 8 keys per step, 8 lanes x 16 B per key row.
 // SELF: keys are positions 0..row_pos of the row's hypothesis, each from physical slot lin[hyp][p].
 // CROSS: keys are the 1500 encoder positions of the hypothesis's window slot.
-template <bool SELF>
+// F8 (cross only): the K/V rows are e4m3 codes converted to their exact bf16 values on load.
+template <bool SELF, bool F8 = false>
 __global__ __launch_bounds__(256) void dec_attn_kernel(DecAttnArgs a) {
+  static_assert(!(SELF && F8), "fp8 panels are cross-attention only");
   __shared__ float s_sc[CT_MAX];
   __shared__ float s_red[4];
   __shared__ float s_acc[4][HD];
@@ -77,6 +122,7 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(DecAttnArgs a) {
   const bf16* K;
   const bf16* V;
   const int* lrow = nullptr;
+  const unsigned char *K8 = nullptr, *V8 = nullptr, *KE = nullptr, *VE = nullptr;
   if (SELF) {
     k0 = 0;
     nk = a.row_pos[row] + 1;
@@ -88,10 +134,20 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(DecAttnArgs a) {
     k0 = split * chunk;
     nk = min(a.T, k0 + chunk) - k0;
     const long long off = ((long long)a.hyp_slot[hyp] * H + h) * ((long long)a.T * HD);
-    K = a.kbase + off;
-    V = a.vbase + off;
+    if constexpr (F8) {
+      K = V = nullptr;                          // (unused: the fp8 form has no bf16 panels)
+      K8 = a.k8 + off + (long long)k0 * HD;
+      V8 = a.v8 + off + (long long)k0 * HD;
+      KE = a.kexp + off / HD + k0;
+      VE = a.vexp + off / HD + k0;
+    } else {
+      K = a.kbase + off;
+      V = a.vbase + off;
+    }
   }
-  if (a.stat && tid == 0) atomicAdd(a.stat + (blockIdx.x & (STAT_SLOTS - 1)), (unsigned long long)(nk * 2 * HD * 2 + 2 * HD * 2));
+  if (a.stat && tid == 0)
+    atomicAdd(a.stat + (blockIdx.x & (STAT_SLOTS - 1)),
+              (unsigned long long)(F8 ? nk * 2 * (HD + 1) + 2 * HD * 2 : nk * 2 * HD * 2 + 2 * HD * 2));
   const long long hstride = (long long)H * a.n_ctx * HD;    // SELF: elements per physical hypothesis
   const int sub = lane & 7, g = lane >> 3;
   float qf[8];
@@ -115,7 +171,8 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(DecAttnArgs a) {
       part[u] = 0.f;
       if (p < nk) {
         float kf[8];
-        load8(krow(K, p) + sub * 8, kf);
+        if constexpr (F8) kv8_load8(K8 + (long long)p * HD + sub * 8, KE[p], kf);
+        else load8(krow(K, p) + sub * 8, kf);
 #pragma unroll
         for (int i = 0; i < 8; ++i) part[u] = fmaf(qf[i], kf[i], part[u]);
       }
@@ -157,7 +214,8 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(DecAttnArgs a) {
       if (p < nk) {
         const float w = s_sc[p];
         float vf[8];
-        load8(krow(V, p) + sub * 8, vf);
+        if constexpr (F8) kv8_load8(V8 + (long long)p * HD + sub * 8, VE[p], vf);
+        else load8(krow(V, p) + sub * 8, vf);
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = fmaf(w, vf[i], acc[i]);
       }
@@ -271,7 +329,7 @@ __device__ __forceinline__ float combine_l2(const float* part_m, const float* pa
 // wave, and every lane issues the K AND V rows of 4 keys before using any (8 x 16 B in flight per lane).
 // Per (row, lane group) an online softmax keeps (m, l, o[8]); groups merge by xor-shuffles, waves through
 // LDS.  With splits > 1 the (m, l, o) partials go to cross_combine_kernel (per row, as the legacy path).
-template <int RG>
+template <int RG, bool F8>
 __device__ __forceinline__ void cross_item(const DecAttnArgs& a, int bx, int split, float (&s_m)[4][RG],
                                            float (&s_l)[4][RG], float (&s_o)[4][RG][HD], float (&s_q)[RG][HD]) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -294,14 +352,26 @@ __device__ __forceinline__ void cross_item(const DecAttnArgs& a, int bx, int spl
   const int k0 = split * chunk;
   const int nk = min(a.T, k0 + chunk) - k0;
   const long long off = ((long long)a.hyp_slot[a.row_hyp[row0]] * H + h) * ((long long)a.T * HD) + (long long)k0 * HD;
-  const bf16* K = a.kbase + off + sub * 8;
-  const bf16* V = a.vbase + off + sub * 8;
+  const bf16* K = F8 ? nullptr : a.kbase + off + sub * 8;      // (F8: no bf16 panels)
+  const bf16* V = F8 ? nullptr : a.vbase + off + sub * 8;
+  // fp8 panels: 8 code bytes per lane and key plus the key's exponent byte, all requested with the chunk's other loads
+  // and converted (exactly) to the bf16 rows below when the chunk is used
+  const unsigned char *K8 = nullptr, *V8 = nullptr, *KE = nullptr, *VE = nullptr;
+  if constexpr (F8) {
+    K8 = a.k8 + off + sub * 8;
+    V8 = a.v8 + off + sub * 8;
+    KE = a.kexp + off / HD;
+    VE = a.vexp + off / HD;
+  }
   if (a.stat && tid == 0)
-    atomicAdd(a.stat + ((bx + split) & (STAT_SLOTS - 1)), (unsigned long long)(nk * 2 * HD * 2 + RG * 2 * HD * 2));
+    atomicAdd(a.stat + ((bx + split) & (STAT_SLOTS - 1)),
+              (unsigned long long)(F8 ? nk * 2 * (HD + 1) + RG * 2 * HD * 2 : nk * 2 * HD * 2 + RG * 2 * HD * 2));
 
   // the first 128-key chunk's K and V rows are requested before the q load (they do not depend on it): one
   // memory round trip for both instead of two in sequence
   bf16x8 kr[4], vr[4];
+  i32x2 kc[4], vc[4];
+  unsigned ke[4], ve[4];
   bool ok[4];
   auto load_chunk = [&](int kb) {
 #pragma unroll
@@ -309,8 +379,15 @@ __device__ __forceinline__ void cross_item(const DecAttnArgs& a, int bx, int spl
       const int p = kb + u * 32 + wv * 8 + g;
       ok[u] = p < nk;
       const int pc = ok[u] ? p : 0;
-      kr[u] = ld_stream(K + (long long)pc * HD);
-      vr[u] = ld_stream(V + (long long)pc * HD);
+      if constexpr (F8) {
+        kc[u] = ld_stream8(K8 + (long long)pc * HD);
+        vc[u] = ld_stream8(V8 + (long long)pc * HD);
+        ke[u] = KE[pc];
+        ve[u] = VE[pc];
+      } else {
+        kr[u] = ld_stream(K + (long long)pc * HD);
+        vr[u] = ld_stream(V + (long long)pc * HD);
+      }
     }
   };
   load_chunk(0);
@@ -368,6 +445,13 @@ __device__ __forceinline__ void cross_item(const DecAttnArgs& a, int bx, int spl
   }
   for (int kb = 0; kb < nk; kb += 128) {
     if (kb > 0) load_chunk(kb);
+    if constexpr (F8) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        kr[u] = __builtin_bit_cast(bf16x8, kv8_bf16x8(kc[u], kv8_scale(ke[u])));
+        vr[u] = __builtin_bit_cast(bf16x8, kv8_bf16x8(vc[u], kv8_scale(ve[u])));
+      }
+    }
 #pragma unroll
     for (int r = 0; r < RG; ++r) {
       float sc[4];
@@ -487,22 +571,22 @@ __device__ __forceinline__ void cross_item(const DecAttnArgs& a, int bx, int spl
 // the plain grid; launched with a capped grid (persistent form) each block takes every gridDim.x-th item, so
 // the kernel holds a bounded number of wave slots per CU and kernels on other streams (the decoder's weight
 // GEMMs) always find room beside it.
-template <int RG>
+template <int RG, bool F8 = false>
 __global__ __launch_bounds__(256) void cross_attn_group_kernel(DecAttnArgs a, int n_items) {
   __shared__ float s_m[4][RG], s_l[4][RG];
   __shared__ float s_o[4][RG][HD];
   __shared__ float s_q[RG][HD];
   for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-    cross_item<RG>(a, it / a.splits, it % a.splits, s_m, s_l, s_o, s_q);
+    cross_item<RG, F8>(a, it / a.splits, it % a.splits, s_m, s_l, s_o, s_q);
     __syncthreads();
   }
 }
 
-template <int RG>
+template <int RG, bool F8>
 static void launch_group(int n_items, int cap, const DecAttnArgs& a, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
   const dim3 grid(cap > 0 ? std::min(n_items, cap) : n_items);
-  if (ev0) hipExtLaunchKernelGGL(cross_attn_group_kernel<RG>, grid, dim3(256), 0, st, ev0, ev1, 0, a, n_items);
-  else hipLaunchKernelGGL(cross_attn_group_kernel<RG>, grid, dim3(256), 0, st, a, n_items);
+  if (ev0) hipExtLaunchKernelGGL((cross_attn_group_kernel<RG, F8>), grid, dim3(256), 0, st, ev0, ev1, 0, a, n_items);
+  else hipLaunchKernelGGL((cross_attn_group_kernel<RG, F8>), grid, dim3(256), 0, st, a, n_items);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -676,7 +760,7 @@ __global__ __launch_bounds__(256) void self_attn_wave_kernel(DecAttnArgs a, int 
 // takes one key and forms all RG dot products, scores to LDS), each row's softmax is formed in LDS and written out
 // for a captured head, then the V panel streams once (pass 3: every row's weighted sum at once).  The per-(row, head)
 // form (dec_attn_kernel) streamed both panels per row: ~2 TB of L2/MALL reads per 150-window large-v3 alignment.
-template <int RG>
+template <int RG, bool F8 = false>
 __global__ __launch_bounds__(256) void cross_capture_kernel(DecAttnArgs a, int group, int bpg) {
   __shared__ float s_sc[RG][CT_MAX];
   __shared__ float s_sum[RG];
@@ -698,9 +782,18 @@ __global__ __launch_bounds__(256) void cross_capture_kernel(DecAttnArgs a, int g
   }
   if (!any) return;
   const long long off = ((long long)a.hyp_slot[hyp0] * H + h) * ((long long)T * HD);
-  const bf16* K = a.kbase + off;
-  const bf16* V = a.vbase + off;
-  if (a.stat && tid == 0) atomicAdd(a.stat + (blockIdx.x & (STAT_SLOTS - 1)), (unsigned long long)(T * 2 * HD * 2 + nr * 2 * HD * 2));
+  const bf16* K = F8 ? nullptr : a.kbase + off;                // (F8: no bf16 panels)
+  const bf16* V = F8 ? nullptr : a.vbase + off;
+  const unsigned char *K8 = nullptr, *V8 = nullptr, *KE = nullptr, *VE = nullptr;
+  if constexpr (F8) {
+    K8 = a.k8 + off;
+    V8 = a.v8 + off;
+    KE = a.kexp + off / HD;
+    VE = a.vexp + off / HD;
+  }
+  if (a.stat && tid == 0)
+    atomicAdd(a.stat + (blockIdx.x & (STAT_SLOTS - 1)),
+              (unsigned long long)(F8 ? T * 2 * (HD + 1) + nr * 2 * HD * 2 : T * 2 * HD * 2 + nr * 2 * HD * 2));
   float qf[RG][8];
 #pragma unroll
   for (int r = 0; r < RG; ++r) {
@@ -717,8 +810,10 @@ __global__ __launch_bounds__(256) void cross_capture_kernel(DecAttnArgs a, int g
   for (int kb = 0; kb < T; kb += 32) {
     const int p = kb + kg;
     float kf[8];
-    if (p < T) load8(K + (long long)p * HD + sub * 8, kf);
-    else {
+    if (p < T) {
+      if constexpr (F8) kv8_load8(K8 + (long long)p * HD + sub * 8, KE[p], kf);
+      else load8(K + (long long)p * HD + sub * 8, kf);
+    } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) kf[i] = 0.f;
     }
@@ -769,7 +864,8 @@ __global__ __launch_bounds__(256) void cross_capture_kernel(DecAttnArgs a, int g
     const int p = kb + kg;
     if (p < T) {
       float vf[8];
-      load8(V + (long long)p * HD + sub * 8, vf);
+      if constexpr (F8) kv8_load8(V8 + (long long)p * HD + sub * 8, VE[p], vf);
+      else load8(V + (long long)p * HD + sub * 8, vf);
 #pragma unroll
       for (int r = 0; r < RG; ++r) {
         const float w = s_sc[r][p];
@@ -821,6 +917,11 @@ __device__ __forceinline__ int tf_vslot(int r, int c) { return r * 64 + ((c ^ ((
 // Key splits (a.splits > 1, no capture): block (window, head, row tile, split) takes tiles [split nt / S, (split+1) nt / S)
 // and writes its (m, l, unnormalised o) partial for cross_combine_kernel, as the VALU kernels do.  This is also the
 // decode path of beam groups (`group` = the window's hypotheses, 2..32 rows padded to one 32-row wave tile).
+// F8: the panels are e4m3 codes with one exponent byte per key (see kv8_* above).  A tile is then 4 KB of K codes + 4 KB
+// of V codes + 64 + 64 exponent bytes: one 16-B code load per thread and panel (key tid / 4, chunks 2 (tid & 3) and
+// 2 (tid & 3) + 1) and the key's exponent byte, all issued together in load_tile; store_tile converts them in registers
+// and writes the same swizzled bf16 LDS image, so everything after LDS is the bf16 kernel.
+template <bool F8 = false>
 __global__ __launch_bounds__(256, 2) void cross_tf_kernel(DecAttnArgs a, int group, int nqt) {
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * 2 * TF_KT * HD];     // [buf][K | V][64 keys][64]
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -865,11 +966,18 @@ __global__ __launch_bounds__(256, 2) void cross_tf_kernel(DecAttnArgs a, int gro
     if (!__syncthreads_or(live)) return;
   }
   const long long off = ((long long)slot * H + h) * ((long long)T * HD);
-  const bf16* K = a.kbase + off;
-  const bf16* V = a.vbase + off;
+  const bf16* K = F8 ? nullptr : a.kbase + off;                // (F8: no bf16 panels)
+  const bf16* V = F8 ? nullptr : a.vbase + off;
+  const unsigned char *K8 = nullptr, *V8 = nullptr, *KE = nullptr, *VE = nullptr;
+  if constexpr (F8) {
+    K8 = a.k8 + off;
+    V8 = a.v8 + off;
+    KE = a.kexp + off / HD;
+    VE = a.vexp + off / HD;
+  }
   const bool cap = hm >= 0;
   if (a.stat && tid == 0)
-    atomicAdd(a.stat + (blockIdx.x & (STAT_SLOTS - 1)), (unsigned long long)((cap ? 3 : 2) * T * HD * 2));
+    atomicAdd(a.stat + (blockIdx.x & (STAT_SLOTS - 1)), (unsigned long long)((cap ? 3 : 2) * T * (F8 ? HD + 1 : HD * 2)));
   const bool valid = r < group;
   const bool live = valid && !done_r;            // output writes only for live rows
   const bool wave_on = qt * 128 + wv * 32 < group;     // wave-uniform: a wave with no row only stages tiles
@@ -877,23 +985,45 @@ __global__ __launch_bounds__(256, 2) void cross_tf_kernel(DecAttnArgs a, int gro
   const int ntt = (T + TF_KT - 1) / TF_KT;
   const int tb = sp * ntt / a.splits, te = (sp + 1) * ntt / a.splits;   // this split's key tiles
   const int nt = te - tb;
-  i32x4 rk[2], rv[2];
+  constexpr int NREG = F8 ? 1 : 2;               // 16-B staging registers per thread and panel
+  i32x4 rk[NREG], rv[NREG];
+  unsigned ek = 0, ev = 0;
   auto load_tile = [&](int t, bool withv) {
+    if constexpr (F8) {
+      const int key = min((tb + t) * TF_KT + (tid >> 2), T - 1), qd = tid & 3;
+      rk[0] = __builtin_nontemporal_load((const i32x4*)(K8 + (long long)key * HD + qd * 16));
+      if (withv) rv[0] = __builtin_nontemporal_load((const i32x4*)(V8 + (long long)key * HD + qd * 16));
+      ek = KE[key];
+      if (withv) ev = VE[key];
+    } else {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int c = tid + i * 256, key = min((tb + t) * TF_KT + (c >> 3), T - 1), ch = c & 7;
-      rk[i] = __builtin_nontemporal_load((const i32x4*)(K + (long long)key * HD + ch * 8));
-      if (withv) rv[i] = __builtin_nontemporal_load((const i32x4*)(V + (long long)key * HD + ch * 8));
+      for (int i = 0; i < 2; ++i) {
+        const int c = tid + i * 256, key = min((tb + t) * TF_KT + (c >> 3), T - 1), ch = c & 7;
+        rk[i] = __builtin_nontemporal_load((const i32x4*)(K + (long long)key * HD + ch * 8));
+        if (withv) rv[i] = __builtin_nontemporal_load((const i32x4*)(V + (long long)key * HD + ch * 8));
+      }
     }
   };
   auto store_tile = [&](int buf, bool withv) {
     bf16* sK = smem + buf * (2 * TF_KT * HD);
     bf16* sV = sK + TF_KT * HD;
+    if constexpr (F8) {
+      const int rr = tid >> 2, ch = 2 * (tid & 3);
+      const float sk = kv8_scale(ek);
+      *(i32x4*)(sK + tf_kslot(rr, ch)) = kv8_bf16x8(i32x2{rk[0][0], rk[0][1]}, sk);
+      *(i32x4*)(sK + tf_kslot(rr, ch + 1)) = kv8_bf16x8(i32x2{rk[0][2], rk[0][3]}, sk);
+      if (withv) {
+        const float sv = kv8_scale(ev);
+        *(i32x4*)(sV + tf_vslot(rr, ch)) = kv8_bf16x8(i32x2{rv[0][0], rv[0][1]}, sv);
+        *(i32x4*)(sV + tf_vslot(rr, ch + 1)) = kv8_bf16x8(i32x2{rv[0][2], rv[0][3]}, sv);
+      }
+    } else {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int c = tid + i * 256, rr = c >> 3, ch = c & 7;
-      *(i32x4*)(sK + tf_kslot(rr, ch)) = rk[i];
-      if (withv) *(i32x4*)(sV + tf_vslot(rr, ch)) = rv[i];
+      for (int i = 0; i < 2; ++i) {
+        const int c = tid + i * 256, rr = c >> 3, ch = c & 7;
+        *(i32x4*)(sK + tf_kslot(rr, ch)) = rk[i];
+        if (withv) *(i32x4*)(sV + tf_vslot(rr, ch)) = rv[i];
+      }
     }
   };
   // (requesting the first tile's K and V before the q load, as cross_item does, measured 2 % slower here: 111.5 vs
@@ -1150,13 +1280,14 @@ __global__ __launch_bounds__(256, 2) void cross_tf_kernel(DecAttnArgs a, int gro
   }
 }
 
+template <bool F8>
 static void launch_k(bool self, dim3 grid, const DecAttnArgs& a, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
   if (ev0) {
     if (self) hipExtLaunchKernelGGL(dec_attn_kernel<true>, grid, dim3(256), 0, st, ev0, ev1, 0, a);
-    else hipExtLaunchKernelGGL(dec_attn_kernel<false>, grid, dim3(256), 0, st, ev0, ev1, 0, a);
+    else hipExtLaunchKernelGGL((dec_attn_kernel<false, F8>), grid, dim3(256), 0, st, ev0, ev1, 0, a);
   } else {
     if (self) hipLaunchKernelGGL(dec_attn_kernel<true>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(dec_attn_kernel<false>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((dec_attn_kernel<false, F8>), grid, dim3(256), 0, st, a);
   }
 }
 
@@ -1186,12 +1317,17 @@ void launch_self_attn(const bf16* q, long long ldq, const bf16* kc, const bf16* 
   WM_LAUNCH_CHECK("self_attn_wave_kernel");
 }
 
-void launch_cross_attn(const bf16* q, long long ldq, const bf16* kbase, const bf16* vbase, int T, const int* hyp_slot,
-                       const int* row_hyp, const int* done, bf16* out, long long ldo, int rows, int H, int group,
-                       float* part_m, float* part_l, float* part_o, float* probs, const int* head_map, int n_align,
-                       int plan_rows, int cap, const CrossFuse& fz, unsigned long long* stat, hipStream_t st,
-                       hipEvent_t ev0, hipEvent_t ev1) {
+// One launcher body for both panel forms: F8 = false reads the bf16 panels kbase / vbase, F8 = true the e4m3 panels of
+// `f8` (same routing, same split rules, the F8 instantiation of the same kernel).
+template <bool F8>
+static void cross_attn_impl(const bf16* q, long long ldq, const bf16* kbase, const bf16* vbase, const CrossKv8& f8, int T,
+                            const int* hyp_slot, const int* row_hyp, const int* done, bf16* out, long long ldo, int rows,
+                            int H, int group, float* part_m, float* part_l, float* part_o, float* probs,
+                            const int* head_map, int n_align, int plan_rows, int cap, const CrossFuse& fz,
+                            unsigned long long* stat, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
   if (rows <= 0) return;
+  if (F8 && (!f8.k || !f8.v || !f8.kexp || !f8.vexp || !hyp_slot))
+    throw std::runtime_error("cross_attn: fp8 panels need codes, exponent bytes and a slot table");
   if (plan_rows < rows) plan_rows = rows;
   if (fz.q_part && fz.q_splits > QMAXS) throw std::runtime_error("cross_attn: too many cq split-K slabs");
   DecAttnArgs a{};
@@ -1200,6 +1336,7 @@ void launch_cross_attn(const bf16* q, long long ldq, const bf16* kbase, const bf
   a.out = out; a.ldo = ldo; a.H = H; a.T = T; a.n_ctx = T;
   a.part_m = part_m; a.part_l = part_l; a.part_o = part_o; a.probs = probs; a.head_map = head_map; a.n_align = n_align;
   a.scale_log2 = 0.125f * 1.4426950408889634f; a.stat = stat;
+  a.k8 = f8.k; a.v8 = f8.v; a.kexp = f8.kexp; a.vexp = f8.vexp;
   // matrix-core form: teacher-forced passes (>= 16 rows per window), and with fz.mfma the decode passes of row groups
   // (beam hypotheses / prefill rows of a window; 2..32 rows)
   const bool mf_tf = fz.tf && group >= 16;
@@ -1224,8 +1361,8 @@ void launch_cross_attn(const bf16* q, long long ldq, const bf16* kbase, const bf
     if (nblk > (1LL << 31) - 1) throw std::runtime_error("cross_attn: grid too large");
     if (splits > 1 && (!part_m || !part_l || !part_o)) throw std::runtime_error("cross_attn: no split scratch");
     hipEvent_t e1 = (splits == 1 || a.cnt) ? ev1 : nullptr;
-    if (ev0) hipExtLaunchKernelGGL(cross_tf_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ev0, e1, 0, a, group, nqt);
-    else hipLaunchKernelGGL(cross_tf_kernel, dim3((unsigned)nblk), dim3(256), 0, st, a, group, nqt);
+    if (ev0) hipExtLaunchKernelGGL(cross_tf_kernel<F8>, dim3((unsigned)nblk), dim3(256), 0, st, ev0, e1, 0, a, group, nqt);
+    else hipLaunchKernelGGL(cross_tf_kernel<F8>, dim3((unsigned)nblk), dim3(256), 0, st, a, group, nqt);
     WM_LAUNCH_CHECK("cross_tf_kernel");
     if (splits > 1 && !a.cnt) {
       if (ev1)
@@ -1247,12 +1384,12 @@ void launch_cross_attn(const bf16* q, long long ldq, const bf16* kbase, const bf
       constexpr int RG = 8;
       const int bpg = (group + RG - 1) / RG;
       const dim3 grid((rows / group) * bpg * H);
-      if (ev0) hipExtLaunchKernelGGL(cross_capture_kernel<RG>, grid, dim3(256), 0, st, ev0, ev1, 0, a, group, bpg);
-      else hipLaunchKernelGGL(cross_capture_kernel<RG>, grid, dim3(256), 0, st, a, group, bpg);
+      if (ev0) hipExtLaunchKernelGGL((cross_capture_kernel<RG, F8>), grid, dim3(256), 0, st, ev0, ev1, 0, a, group, bpg);
+      else hipLaunchKernelGGL((cross_capture_kernel<RG, F8>), grid, dim3(256), 0, st, a, group, bpg);
       WM_LAUNCH_CHECK("cross_capture_kernel");
       return;
     }
-    launch_k(false, dim3(rows * H, 1), a, st, ev0, ev1);
+    launch_k<F8>(false, dim3(rows * H, 1), a, st, ev0, ev1);
     WM_LAUNCH_CHECK("dec_attn_kernel<cross>");
     return;
   }
@@ -1276,14 +1413,14 @@ void launch_cross_attn(const bf16* q, long long ldq, const bf16* kbase, const bf
   // events (profiler): start on the attention kernel, stop on the last kernel of the pair
   hipEvent_t e0 = ev0, e1 = (splits == 1 || fz.cnt) ? ev1 : nullptr;
   switch (rg) {
-    case 1: launch_group<1>(n_items, cap, a, st, e0, e1); break;
-    case 2: launch_group<2>(n_items, cap, a, st, e0, e1); break;
-    case 3: launch_group<3>(n_items, cap, a, st, e0, e1); break;
-    case 4: launch_group<4>(n_items, cap, a, st, e0, e1); break;
-    case 5: launch_group<5>(n_items, cap, a, st, e0, e1); break;
-    case 6: launch_group<6>(n_items, cap, a, st, e0, e1); break;
-    case 7: launch_group<7>(n_items, cap, a, st, e0, e1); break;
-    default: launch_group<8>(n_items, cap, a, st, e0, e1); break;
+    case 1: launch_group<1, F8>(n_items, cap, a, st, e0, e1); break;
+    case 2: launch_group<2, F8>(n_items, cap, a, st, e0, e1); break;
+    case 3: launch_group<3, F8>(n_items, cap, a, st, e0, e1); break;
+    case 4: launch_group<4, F8>(n_items, cap, a, st, e0, e1); break;
+    case 5: launch_group<5, F8>(n_items, cap, a, st, e0, e1); break;
+    case 6: launch_group<6, F8>(n_items, cap, a, st, e0, e1); break;
+    case 7: launch_group<7, F8>(n_items, cap, a, st, e0, e1); break;
+    default: launch_group<8, F8>(n_items, cap, a, st, e0, e1); break;
   }
   WM_LAUNCH_CHECK("cross_attn_group_kernel");
   if (splits > 1 && !fz.cnt) {
@@ -1295,4 +1432,105 @@ void launch_cross_attn(const bf16* q, long long ldq, const bf16* kbase, const bf
                          out, ldo, H, splits);
     WM_LAUNCH_CHECK("cross_combine_kernel");
   }
+}
+
+void launch_cross_attn(const bf16* q, long long ldq, const bf16* kbase, const bf16* vbase, int T, const int* hyp_slot,
+                       const int* row_hyp, const int* done, bf16* out, long long ldo, int rows, int H, int group,
+                       float* part_m, float* part_l, float* part_o, float* probs, const int* head_map, int n_align,
+                       int plan_rows, int cap, const CrossFuse& fz, unsigned long long* stat, hipStream_t st,
+                       hipEvent_t ev0, hipEvent_t ev1) {
+  cross_attn_impl<false>(q, ldq, kbase, vbase, CrossKv8{}, T, hyp_slot, row_hyp, done, out, ldo, rows, H, group, part_m,
+                         part_l, part_o, probs, head_map, n_align, plan_rows, cap, fz, stat, st, ev0, ev1);
+}
+
+void launch_cross_attn_fp8(const bf16* q, long long ldq, const CrossKv8& kv, int T, const int* hyp_slot,
+                           const int* row_hyp, const int* done, bf16* out, long long ldo, int rows, int H, int group,
+                           float* part_m, float* part_l, float* part_o, float* probs, const int* head_map, int n_align,
+                           int plan_rows, int cap, const CrossFuse& fz, unsigned long long* stat, hipStream_t st,
+                           hipEvent_t ev0, hipEvent_t ev1) {
+  cross_attn_impl<true>(q, ldq, nullptr, nullptr, kv, T, hyp_slot, row_hyp, done, out, ldo, rows, H, group, part_m,
+                        part_l, part_o, probs, head_map, n_align, plan_rows, cap, fz, stat, st, ev0, ev1);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Quantiser of the fp8 cross K/V panels (include/whisper_mi355.h wm_cross_kv_fp8_quantize has the definition).  8 lanes
+// per 64-value row (16 B each), 8 rows per wave, 32 per block.  The row maximum is an integer maximum of the bf16
+// magnitudes (monotone for non-negative floats, and blind to denormal flushing) reduced over the row's 8 lanes by
+// xor-shuffles; e comes from its exponent and mantissa bits.  x * 2^-e is exact wherever the rounding is decided, the
+// hardware conversion rounds to nearest even, and the product is clamped to +-448 first (only the upper clamp of e can
+// leave it larger).  A wave stores its 8 code rows as 512 contiguous bytes; exponent bytes are plain byte stores.
+// Source row r lands in destination row (r / src_per) * dst_stride + dst_off + r % src_per: the staging chunk
+// [L][2][chunk][H][T] of wm_cross_kv into the slot panels [L][2][n_slots][H][T].
+// DEQ (cross_kv_fp8 = 2, the reference form): the same codes, stored dequantised as bf16 by the attention kernels' own
+// conversion, so both forms hold the same values by construction.
+#define KV8_ROWS_PER_BLOCK 32
+template <bool DEQ>
+__global__ __launch_bounds__(256) void kv8_quant_kernel(const bf16* __restrict__ src, long long n_rows, long long src_per,
+                                                        long long dst_stride, long long dst_off,
+                                                        unsigned char* __restrict__ codes, unsigned char* __restrict__ exps,
+                                                        bf16* __restrict__ deq) {
+  const int tid = threadIdx.x, sub = tid & 7;
+  const long long r = (long long)blockIdx.x * KV8_ROWS_PER_BLOCK + (tid >> 3);
+  const bool in = r < n_rows;
+  const long long rc = in ? r : n_rows - 1;                   // (clamped: the shuffles below want every lane)
+  const i32x4 raw = *(const i32x4*)(src + rc * HD + sub * 8);
+  unsigned amax = 0, bad = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned lo = (unsigned)raw[i] & 0x7fffu, hi = ((unsigned)raw[i] >> 16) & 0x7fffu;
+    amax = max(amax, max(lo, hi));
+    bad |= (lo >= 0x7f80u) | (hi >= 0x7f80u);
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    amax = max(amax, (unsigned)__shfl_xor((int)amax, o, 64));
+    bad |= (unsigned)__shfl_xor((int)bad, o, 64);
+  }
+  int e = 0;
+  i32x2 c{0, 0};
+  if (bad) {
+    c = i32x2{0x7f7f7f7f, 0x7f7f7f7f};
+  } else if (amax != 0) {
+    // amax = m 2^k, 1 <= m < 2; 448 = 1.75 2^8: the smallest e with amax 2^-e <= 448
+    const int k = (int)(amax >> 7) - 127;
+    e = (amax & 0x7fu) <= 0x60u ? k - 8 : k - 7;
+    e = min(110, max(-110, e));
+    const float inv = __uint_as_float((unsigned)(127 - e) << 23);
+    float f[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[2 * i] = __uint_as_float((unsigned)raw[i] << 16) * inv;
+      f[2 * i + 1] = __uint_as_float((unsigned)raw[i] & 0xffff0000u) * inv;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = fminf(fmaxf(f[i], -448.0f), 448.0f);
+    int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
+    int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
+    c = i32x2{w0, w1};
+  }
+  if (!in) return;
+  const long long d = (r / src_per) * dst_stride + dst_off + r % src_per;
+  if constexpr (DEQ) {
+    *(i32x4*)(deq + d * HD + sub * 8) = kv8_bf16x8(c, kv8_scale((unsigned)(e + 127)));
+  } else {
+    *(i32x2*)(codes + d * HD + sub * 8) = c;
+    if (sub == 0) exps[d] = (unsigned char)(e + 127);
+  }
+}
+
+void launch_kv8_quant(const bf16* src, long long n_rows, long long src_per, long long dst_stride, long long dst_off,
+                      unsigned char* codes, unsigned char* exps, bf16* deq, hipStream_t st) {
+  if (n_rows <= 0) return;
+  if (src_per <= 0) throw std::runtime_error("kv8_quant: bad row mapping");
+  const long long nb = (n_rows + KV8_ROWS_PER_BLOCK - 1) / KV8_ROWS_PER_BLOCK;
+  if (nb > (1LL << 31) - 1) throw std::runtime_error("kv8_quant: grid too large");
+  if (deq)
+    hipLaunchKernelGGL(kv8_quant_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, src, n_rows, src_per, dst_stride,
+                       dst_off, codes, exps, deq);
+  else
+    hipLaunchKernelGGL(kv8_quant_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, src, n_rows, src_per, dst_stride,
+                       dst_off, codes, exps, deq);
+  WM_LAUNCH_CHECK("kv8_quant_kernel");
 }

@@ -66,6 +66,15 @@ struct CrossFuse {
                                    // the last-arriving split in-kernel (nullptr: separate combine kernel)
 };
 
+// fp8 cross K/V panels of one layer (engine option cross_kv_fp8; attn_dec.hip launch_cross_attn_fp8): OCP e4m3 codes
+// [slots][H][T][64] and one exponent byte per 64-code row [slots][H][T], value = e4m3(code) * 2^(byte - 127).
+struct CrossKv8 {
+  const unsigned char* k = nullptr;
+  const unsigned char* v = nullptr;
+  const unsigned char* kexp = nullptr;
+  const unsigned char* vexp = nullptr;
+};
+
 // Launch check used by every host-side launcher: converts an asynchronous launch failure into an
 // exception the C-ABI layer turns into an error code + wm_last_error() text.
 #define WM_LAUNCH_CHECK(what)                                                                  \

@@ -238,6 +238,17 @@ struct wm_engine {
   DevBuf xenc;               // factored: [n_slots][T][d] bf16 encoder outputs (cross_fp8: OCP e4m3 bytes)
   DevBuf xscale;             // cross_fp8: [n_slots][T] f32 per-position scales
   int cross_fp8 = 0;         // opt-in fp8 cross memory (factored form only; changes numerics, never the default)
+  // opt-in fp8 K/V panels of the PROJECTED form (independent of cross_fp8; changes numerics, never the default):
+  //   0  bf16 panels in ckv
+  //   1  ckv holds e4m3 codes [L][2][n_slots][H][T][64] bytes, ckv_exp one exponent byte per 64-code row
+  //      [L][2][n_slots][H][T]; the attention kernels' F8 instantiations convert on load (attn_dec.hip)
+  //   2  reference form: bf16 panels holding the dequantised values of form 1, read by the bf16 kernels
+  // Forms 1 and 2: wm_cross_kv projects KV8_STAGE_WINDOWS windows at a time into kv8_stage (bf16, panel layout) and
+  // the quantiser writes their slots.
+  int cross_kv_fp8 = 0;
+  DevBuf ckv_exp, kv8_stage;
+  static constexpr int KV8_STAGE_WINDOWS = 2;   // at most 2 x 245.8 MB = 491.5 MB of staging at large-v3 (a call of
+                                                // one window stages one)
   DevBuf xwkt;               // factored: Wk^T per layer and head [L][H][d][64] bf16, packed from dec.ckv.w
   DevBuf xwvb;               // factored: Wv per layer and head in 16-column blocks [L][H][d/16][64][16]
   bool xwkt_ready = false;
@@ -282,7 +293,7 @@ struct wm_engine {
 
   size_t device_bytes() const {
     size_t t = arena.bytes;
-    for (const DevBuf* b : {&e_cols, &e_h1, &e_x, &e_hb, &e_qkv, &e_ao, &e_ff, &ckv, &xenc, &xscale, &xwkt, &xwvb, &s_qp, &s_pu, &skv, &s_x, &s_hb, &s_q, &s_ao,
+    for (const DevBuf* b : {&e_cols, &e_h1, &e_x, &e_hb, &e_qkv, &e_ao, &e_ff, &ckv, &ckv_exp, &kv8_stage, &xenc, &xscale, &xwkt, &xwvb, &s_qp, &s_pu, &skv, &s_x, &s_hb, &s_q, &s_ao,
                             &s_ff, &s_logits, &s_pm, &s_pl, &s_po, &d_tokens, &d_lin, &d_fin_tok})
       t += b->bytes;
     return t;
@@ -569,6 +580,7 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
   const size_t ckv_layer = (size_t)e->n_slots * H * T * 64;
   bf16* skv = e->skv.as<bf16>();
   bf16* ckv = e->ckv.as<bf16>();
+  const size_t cexp_layer = (size_t)e->n_slots * H * T;            // fp8 panels: exponent bytes per (layer, k|v)
   const auto& W = dec_weights(e)[l];
   const size_t wsb = 64ull << 20;
   sl.ws->ensure(wsb);
@@ -744,6 +756,20 @@ void decoder_layer(wm_engine* e, const DecSlice& sl, int l, const int* row_pos, 
       ProfScope ps(e, P_CROSS_COMB, st, 2.0 * rows * d * d, 2.0 * d * d + 2.0 * splits * rows * prow + 2.0 * rows * d);
       launch_xcomb_vo(pu, pml, splits, sl.total_rows, wv, bv, row_hyp, done, ao, d, rows, H, d, T, probs, hmap, n_align, st);
     }
+  } else if (e->cross_kv_fp8 == 1) {
+    // projected form, fp8 panels: same launcher rules on the F8 kernel instantiations
+    const size_t po = (size_t)r0 * H * 16;
+    const unsigned char* c8 = e->ckv.as<unsigned char>();
+    const unsigned char* x8 = e->ckv_exp.as<unsigned char>();
+    CrossKv8 kv;
+    kv.k = c8 + (size_t)(2 * l) * ckv_layer;
+    kv.v = c8 + (size_t)(2 * l + 1) * ckv_layer;
+    kv.kexp = x8 + (size_t)(2 * l) * cexp_layer;
+    kv.vexp = x8 + (size_t)(2 * l + 1) * cexp_layer;
+    ProfScope ps(e, P_CROSS_ATTN, st, 0, 0, true);
+    launch_cross_attn_fp8(q, d, kv, T, e->d_hyp_slot.as<int>(), row_hyp, done, ao, d, rows, H, cross_group,
+                          e->s_pm.as<float>() + po, e->s_pl.as<float>() + po, e->s_po.as<float>() + po * 64, probs, hmap,
+                          n_align, sl.total_rows, e->cross_cap, fz, e->dstat(P_CROSS_ATTN), st, ps.a, ps.b);
   } else {
     const size_t po = (size_t)r0 * H * 16;
     ProfScope ps(e, P_CROSS_ATTN, st, 0, 0, true);
@@ -874,12 +900,17 @@ void reserve(wm_engine* e, int n_slots, int n_hyp) {
   if (n_slots > e->n_slots) {
     // factored mode keeps each window's encoder output (T x d bf16); projected mode its L x 2 K/V panels
     e->ckv.release();
+    e->ckv_exp.release();
+    e->kv8_stage.release();
     e->xenc.release();
     e->xscale.release();
     if (e->cross_mode == 1) {
       // bf16: tile-blocked slots (attn_xenc.hip xblock_kernel), T padded to whole 32-row tiles
       e->xenc.ensure(e->cross_fp8 ? (size_t)n_slots * T * m.n_state : (size_t)n_slots * xblock_slot_elems(T, m.n_state) * 2);
       if (e->cross_fp8) e->xscale.ensure((size_t)n_slots * T * 4);
+    } else if (e->cross_kv_fp8 == 1) {
+      e->ckv.ensure((size_t)L * 2 * n_slots * H * T * 64);
+      e->ckv_exp.ensure((size_t)L * 2 * n_slots * H * T);
     } else {
       e->ckv.ensure((size_t)L * 2 * n_slots * H * T * 64 * 2);
     }
@@ -2333,7 +2364,7 @@ void require_weights(wm_engine* e) {
   e->weights_ok = true;
 }
 
-// cross_mode / cross_fp8: switching re-allocates the window slots in the new form (their contents are dropped: run
+// cross_mode / cross_fp8 / cross_kv_fp8: switching re-allocates the window slots in the new form (their contents are dropped: run
 // wm_cross_kv again)
 void set_cross_form(wm_engine* e, int* field, int v) {
   if (v == *field) return;
@@ -2342,7 +2373,12 @@ void set_cross_form(wm_engine* e, int* field, int v) {
   const int n = e->n_slots;
   e->n_slots = 0;
   if (n > 0) reserve(e, n, e->n_hyp_cap);
-  else { e->ckv.release(); e->xenc.release(); e->xscale.release(); }
+  else { e->ckv.release(); e->ckv_exp.release(); e->kv8_stage.release(); e->xenc.release(); e->xscale.release(); }
+}
+
+void set_cross_kv_fp8(wm_engine* e, int64_t v) {
+  if (v < 0 || v > 2) throw std::runtime_error("wm_set_option: cross_kv_fp8 is 0 (bf16 panels), 1 (fp8 panels) or 2 (reference form)");
+  set_cross_form(e, &e->cross_kv_fp8, (int)v);
 }
 
 void set_dec_plan_preset(wm_engine* e, int64_t v) {
@@ -2393,6 +2429,7 @@ const OptRow kOptions[] = {
      OPT_SET(if (v != 72 && v != 144) throw std::runtime_error("decode_gemm_big_lds: 72 or 144"); e->dec_big_lds = (int)v)},
     {"cross_mode", "VLOG_AMD_CROSS_MODE", OPT_GET(e->cross_mode), OPT_SET(set_cross_form(e, &e->cross_mode, v ? 1 : 0))},
     {"cross_fp8", "VLOG_AMD_CROSS_FP8", OPT_GET(e->cross_fp8), OPT_SET(set_cross_form(e, &e->cross_fp8, v ? 1 : 0))},
+    {"cross_kv_fp8", "VLOG_AMD_CROSS_KV_FP8", OPT_GET(e->cross_kv_fp8), OPT_SET(set_cross_kv_fp8(e, v))},
     {"cross_attn_blocks", "VLOG_AMD_CROSS_BLOCKS", OPT_GET(e->cross_cap), OPT_SET(e->cross_cap = (int)clamp64(v, 0, INT32_MAX))},
     {"cross_attn_fuse", "VLOG_AMD_CROSS_FUSE", OPT_GET(e->cross_fuse), OPT_SET(e->cross_fuse = (int)(v & 3))},
     {"cross_attn_snake", "VLOG_AMD_XSNAKE", OPT_GET(e->xsnake), OPT_SET(e->xsnake = v != 0)},
@@ -2568,7 +2605,7 @@ void wm_destroy(wm_engine* e) {
   (void)hipDeviceSynchronize();
   for (DevBuf* b : {&e->arena, &e->fe_window, &e->fe_cos, &e->fe_sin, &e->fe_filt, &e->fe_lo, &e->fe_hi, &e->e_cols,
                     &e->e_h1, &e->e_x, &e->e_hb, &e->e_qkv, &e->e_ao, &e->e_ff, &e->e_seek, &e->e_len, &e->ckv,
-                    &e->skv, &e->d_tokens, &e->d_lin, &e->d_seq_len, &e->d_done, &e->d_cum, &e->d_row_tok,
+                    &e->ckv_exp, &e->kv8_stage, &e->skv, &e->d_tokens, &e->d_lin, &e->d_seq_len, &e->d_done, &e->d_cum, &e->d_row_tok,
                     &e->d_row_pos, &e->d_row_hyp, &e->d_hyp_slot, &e->d_n_active, &e->d_suppress, &e->d_cand_tok,
                     &e->d_cand_lp, &e->d_fin_tok, &e->d_fin_len, &e->d_fin_cum, &e->d_n_fin, &e->d_ns,
                     &e->d_logit_rows, &e->d_prow_tok, &e->d_prow_pos, &e->d_prow_hyp, &e->d_head_map, &e->s_x,
@@ -2698,6 +2735,29 @@ int wm_cross_kv(wm_engine* e, const void* d_enc, int32_t B, int32_t slot0, void*
                     (hipStream_t)stream);
       return;
     }
+    if (e->cross_kv_fp8) {
+      // fp8 panels (1) / their dequantised reference form (2): the same GEMM projects KV8_STAGE_WINDOWS windows at a
+      // time into the bf16 staging buffer in the panel layout, the quantiser writes that chunk's slots
+      hipStream_t st = (hipStream_t)stream;
+      const int H = m.n_head, L = m.n_dec_layer;
+      const long long win_rows = (long long)H * T;                       // 64-value rows per (layer, k|v, window)
+      constexpr int CW = wm_engine::KV8_STAGE_WINDOWS;
+      // (sized to this call's chunk: a one-window call, the sequential transcribe, stages one window)
+      e->kv8_stage.ensure((size_t)L * 2 * std::min(CW, (int)B) * win_rows * 64 * 2);
+      for (int b0 = 0; b0 < B; b0 += CW) {
+        const int nb = std::min(CW, B - b0);
+        GemmEpi ep = epi_of(EPI_CROSS_KV, e->kv8_stage.p, 0, e->Wf("dec.ckv.b"));
+        ep.rpb = T; ep.d = d; ep.head_dim = 64; ep.n_head = H; ep.n_slots = nb; ep.slot0 = 0;
+        gemm_p(e, P_CROSSKV_GEMM, amat((const bf16*)d_enc + (size_t)b0 * T * d, d), e->Wb("dec.ckv.w"), d, nb * T, L * 2 * d,
+               d, ep, st);
+        const long long n_rows = (long long)L * 2 * nb * win_rows;
+        ProfScope ps(e, P_CROSSKV_GEMM, st, 0, (e->cross_kv_fp8 == 1 ? 193.0 : 256.0) * n_rows);
+        launch_kv8_quant(e->kv8_stage.as<bf16>(), n_rows, nb * win_rows, (long long)e->n_slots * win_rows,
+                         (long long)(slot0 + b0) * win_rows, e->ckv.as<unsigned char>(), e->ckv_exp.as<unsigned char>(),
+                         e->cross_kv_fp8 == 2 ? e->ckv.as<bf16>() : nullptr, st);
+      }
+      return;
+    }
     GemmEpi ep = epi_of(EPI_CROSS_KV, e->ckv.p, 0, e->Wf("dec.ckv.b"));
     ep.rpb = T; ep.d = d; ep.head_dim = 64; ep.n_head = m.n_head; ep.n_slots = e->n_slots; ep.slot0 = slot0;
     gemm_p(e, P_CROSSKV_GEMM, amat((const bf16*)d_enc, d), e->Wb("dec.ckv.w"), d, B * T, m.n_dec_layer * 2 * d, d, ep,
@@ -2819,6 +2879,16 @@ int wm_resample(wm_engine* e, const void* d_src, int32_t fmt, int32_t channels, 
 int wm_cross_fp8_quantize(wm_engine* e, const void* d_enc, int64_t rows, uint8_t* d_codes, float* d_scale, void* stream) {
   return guarded(e, [&] {
     launch_xquant8((const bf16*)d_enc, rows, e->dm.n_state, d_codes, d_scale, (hipStream_t)stream);
+  });
+}
+
+int wm_cross_kv_fp8_quantize(wm_engine* e, const void* d_rows_bf16, int64_t n_rows, uint8_t* d_codes, uint8_t* d_exp,
+                             void* stream) {
+  return guarded(e, [&] {
+    if (n_rows < 0) throw std::runtime_error("wm_cross_kv_fp8_quantize: negative row count");
+    if (n_rows == 0) return;
+    if (!d_rows_bf16 || !d_codes || !d_exp) throw std::runtime_error("wm_cross_kv_fp8_quantize: null buffer");
+    launch_kv8_quant((const bf16*)d_rows_bf16, n_rows, n_rows, n_rows, 0, d_codes, d_exp, nullptr, (hipStream_t)stream);
   });
 }
 

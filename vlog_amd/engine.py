@@ -201,6 +201,27 @@ class GpuEngine:
                                                     self.stream_ptr()), "wm_cross_fp8_quantize")
         return codes, scale
 
+    def cross_kv_fp8_quantize(self, rows: torch.Tensor, codes: Optional[torch.Tensor] = None,
+                              exps: Optional[torch.Tensor] = None):
+        """wm_cross_kv_fp8_quantize on bf16 rows [..., 64] -> (uint8 codes [n][64], uint8 exponent bytes [n]), device
+        tensors (the projected form's fp8 K/V panels, option cross_kv_fp8).  `codes` / `exps`: write into these
+        (contiguous uint8 device tensors of n * 64 / n elements, e.g. views inside guarded buffers)."""
+        if rows.dtype != torch.bfloat16 or rows.shape[-1] != 64:
+            raise ValueError("cross_kv_fp8_quantize: rows of 64 bf16 values")
+        x = rows.reshape(-1, 64).contiguous()
+        n = x.shape[0]
+        if codes is None:
+            codes = torch.empty((n, 64), dtype=torch.uint8, device=self.device)
+        if exps is None:
+            exps = torch.empty(n, dtype=torch.uint8, device=self.device)
+        if codes.numel() != n * 64 or exps.numel() != n or not codes.is_contiguous() or not exps.is_contiguous():
+            raise ValueError("cross_kv_fp8_quantize: output sizes")
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.wm_cross_kv_fp8_quantize(self.h, C.c_void_p(x.data_ptr()), n,
+                                                          C.c_void_p(codes.data_ptr()), C.c_void_p(exps.data_ptr()),
+                                                          self.stream_ptr()), "wm_cross_kv_fp8_quantize")
+        return codes, exps
+
     def set_option(self, key: str, value: int) -> None:
         """Engine scheduling knob (wm_set_option), e.g. set_option("decode_split", 0)."""
         _capi.check(self.lib.wm_set_option(self.h, key.encode(), int(value)), "wm_set_option")

@@ -257,7 +257,9 @@ class WhisperModel:
         over the encoder output; half the bytes of K and V) for one row, the projected K/V form when several
         rows share a window (beam search: every row of the group reads the window's K/V panels once, while the
         factored kernel re-reads the encoder output per 32 (row, head) pairs).  The opt-in fp8
-        cross memory is a factored-form mode and is never overridden; VLOG_AMD_CROSS_AUTO=0 disables the choice."""
+        cross memory is a factored-form mode and is never overridden; VLOG_AMD_CROSS_AUTO=0 disables the choice.
+        The projected form's own fp8 option (cross_kv_fp8 / VLOG_AMD_CROSS_KV_FP8) leaves the choice on: beam groups
+        then read fp8 K/V panels and one-row decodes the factored bf16 form."""
         if os.environ.get("VLOG_AMD_CROSS_AUTO", "1") == "0" or self.engine.option("cross_fp8", 0):
             return
         self.engine.set_option("cross_mode", 0 if rows_per_window > 1 else 1)
