@@ -255,6 +255,29 @@ typedef struct wm_generate_args {
  * call (-1, wm_last_error names the window and step) instead of emitting a token. */
 int wm_generate(wm_engine* e, const wm_generate_args* a, void* stream);
 
+/* Sequence bias: the third rule over each hypothesis' GENERATED tokens (transformers' SequenceBiasLogitsProcessor):
+ * custom-vocabulary boosts and soft or hard bans.  The table has n entries; entry j is the token sequence
+ * h_tokens[h_off[j] .. h_off[j+1]) of 1 .. 16 ids inside the vocabulary, with the finite bias h_bias[j].  At a
+ * decode step of a hypothesis with G generated tokens (the tokens after that window's own prompt: never the prompt,
+ * previous text, prefix or hotwords), entry j of length n_j is active iff n_j - 1 <= G and the last n_j - 1
+ * generated tokens equal the entry's first n_j - 1 ids (entries of length 1 are always active); every active entry
+ * adds its bias to the logit of its LAST id.  Active entries that end in one id add up in entry order (f32, the sum
+ * first, then the logit), so a run is reproducible bit for bit; duplicates are allowed.  Only the completing token is
+ * biased: to favour a multi-token name from its first token, list its prefixes as entries of their own.
+ * Order: repetition penalty, sequence bias, no-repeat n-gram mask, then suppression, blank and timestamp rules.  So
+ * the bias feeds the timestamp forcing and the log-prob normaliser: h_scores, h_cum_logprob, the per-step records
+ * and the beam ranking are those of the BIASED distribution.  A mask wins over a bias (a masked id stays masked).
+ * The table belongs to the engine: it holds for every later wm_generate, in all decode forms (greedy, sampling,
+ * beam, the row-set decodes, ragged prompts), until it is replaced; n = 0 clears it (the pointers may be NULL), and
+ * an engine without a table launches exactly the kernels it launched before this entry point existed.
+ * The call fails (-1, nothing launched, wm_last_error names the entry) on n > 1024, offsets that do not start at 0
+ * or do not ascend, an empty entry or one of more than 16 tokens, an id outside the vocabulary or a non-finite
+ * bias; the previous table then stays in place and the engine usable.  The upload is ordered on `stream` and
+ * complete when the call returns.  No per-step launch is added.  (Added without an ABI bump: a new entry point,
+ * wm_generate_args unchanged.) */
+int wm_set_sequence_bias(wm_engine* e, int32_t n, const int32_t* h_off /* [n + 1] */, const int32_t* h_tokens,
+                         const float* h_bias /* [n] */, void* stream);
+
 /* Teacher-forced decoder forward over n_seq sequences of seq_len tokens (one window slot each): logits for
  * every position (d_logits f32 [n_seq*seq_len][n_vocab]) or only the last (last_only: [n_seq][n_vocab]).
  * Optional cross-attention capture for word alignment (ctranslate2 Whisper.align [FW↑]): for each of

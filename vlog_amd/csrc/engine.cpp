@@ -175,6 +175,10 @@ struct wm_engine {
   DevBuf d_win_prompt, d_win_slot, d_hyp_out, d_res_tok, d_res_len, d_res_cum, d_res_ns, d_res_lp, d_res_lp_o, d_ev;
   DevBuf d_hyp_begin, d_hyp_maxlen, d_win_len, d_win_maxlen;   // ragged prompts (search.h hyp_begin / hyp_maxlen)
   std::vector<int> h_ev;     // host image of d_ev (kept alive until the next poll syncs the stream)
+  // sequence-bias table (wm_set_sequence_bias; search.h bias_*): allocated once at the limits' size, so a captured
+  // step graph's pointers stay valid whatever table follows
+  DevBuf d_sb_off, d_sb_tok, d_sb_val;
+  int n_seq_bias = 0;
   int dbg_nan_row = -1;      // TEST ONLY (wm_set_option "debug_nan_row"): NaN logits row before every selection
   int dbg_nan_count = 1;     // TEST ONLY ("debug_nan_count"): rows [debug_nan_row, + count) (a whole beam group: nlive 0)
   // step activations
@@ -980,6 +984,10 @@ SearchParams search_params(wm_engine* e, const wm_generate_args* a, float* logit
   // captured step graph, which is safe: every StepGraph lives inside one wm_generate call and is never reused.
   sp.rep_penalty = a->repetition_penalty == 0.f ? 1.0f : a->repetition_penalty;
   sp.no_repeat_ngram = a->no_repeat_ngram_size;
+  if (e->n_seq_bias > 0) {
+    sp.bias_off = e->d_sb_off.as<int>(); sp.bias_tok = e->d_sb_tok.as<int>(); sp.bias_val = e->d_sb_val.as<float>();
+    sp.n_bias = e->n_seq_bias;
+  }
   return sp;
 }
 
@@ -2614,7 +2622,8 @@ void wm_destroy(wm_engine* e) {
                     &e->a_next, &e->a_probs, &e->a_rowsum, &e->a_z, &e->a_mat, &e->a_cost, &e->a_trace, &e->a_pi,
                     &e->a_pj, &e->a_plen, &e->a_meta, &e->a_enc, &e->a_kv, &e->d_tok_lp, &e->d_tok_lp_o, &e->d_fin_lp, &e->d_win_prompt,
                     &e->d_win_slot, &e->d_hyp_out, &e->d_res_tok, &e->d_res_len, &e->d_res_cum, &e->d_res_ns, &e->d_res_lp,
-                    &e->d_res_lp_o, &e->d_ev, &e->d_hyp_begin, &e->d_hyp_maxlen, &e->d_win_len, &e->d_win_maxlen})
+                    &e->d_res_lp_o, &e->d_ev, &e->d_hyp_begin, &e->d_hyp_maxlen, &e->d_win_len, &e->d_win_maxlen,
+                    &e->d_sb_off, &e->d_sb_tok, &e->d_sb_val})
     b->release();
   for (auto& kv : e->rs_taps) kv.second.pp.release();
   if (e->st2) (void)hipStreamDestroy(e->st2);
@@ -2946,6 +2955,57 @@ int wm_dtw_open(wm_engine* e, const float* d_cost, int32_t n, int32_t m, int32_t
   return guarded(e, [&] {
     if (!h_rows) throw std::runtime_error("wm_dtw_open: null h_rows");
     dtw_run(e, d_cost, n, m, h_text_idx, h_time_idx, h_path_len, (hipStream_t)stream, h_rows);
+  });
+}
+
+int wm_set_sequence_bias(wm_engine* e, int32_t n, const int32_t* h_off, const int32_t* h_tokens, const float* h_bias,
+                         void* stream) {
+  return guarded(e, [&] {
+    const std::string who = "wm_set_sequence_bias: ";
+    if (n < 0 || n > SEARCH_BIAS_MAX)
+      throw std::runtime_error(who + "n must be in [0, " + std::to_string(SEARCH_BIAS_MAX) + "]");
+    if (n == 0) {
+      e->n_seq_bias = 0;
+      return;
+    }
+    if (!h_off || !h_tokens || !h_bias) throw std::runtime_error(who + "null table");
+    // everything is validated before the engine's table is touched: a refused call leaves the previous one in place
+    if (h_off[0] != 0) throw std::runtime_error(who + "offsets must start at 0");
+    for (int j = 0; j < n; ++j) {
+      const std::string ent = "entry " + std::to_string(j);
+      const long long nj = (long long)h_off[j + 1] - h_off[j];
+      if (nj < 1 || nj > SEARCH_BIAS_LEN)
+        throw std::runtime_error(who + ent + " has " + std::to_string(nj) + " tokens (offsets must ascend by 1 .. " +
+                                 std::to_string(SEARCH_BIAS_LEN) + ")");
+      for (int i = h_off[j]; i < h_off[j + 1]; ++i)
+        if (h_tokens[i] < 0 || h_tokens[i] >= e->dm.n_vocab)
+          throw std::runtime_error(who + ent + " holds token " + std::to_string(h_tokens[i]) + " outside the vocabulary");
+      if (!std::isfinite(h_bias[j])) throw std::runtime_error(who + ent + " has a non-finite bias");
+    }
+    // device order: by completing id, entries of one id in the caller's order (search.hip header)
+    std::vector<int> order(n);
+    for (int j = 0; j < n; ++j) order[j] = j;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int a, int b) { return h_tokens[h_off[a + 1] - 1] < h_tokens[h_off[b + 1] - 1]; });
+    std::vector<int> off(n + 1, 0), tok;
+    std::vector<float> val(n);
+    tok.reserve(h_off[n]);
+    for (int r = 0; r < n; ++r) {
+      const int j = order[r];
+      tok.insert(tok.end(), h_tokens + h_off[j], h_tokens + h_off[j + 1]);
+      off[r + 1] = (int)tok.size();
+      val[r] = h_bias[j];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    e->d_sb_off.ensure((size_t)(SEARCH_BIAS_MAX + 1) * 4);
+    e->d_sb_tok.ensure((size_t)SEARCH_BIAS_MAX * SEARCH_BIAS_LEN * 4);
+    e->d_sb_val.ensure((size_t)SEARCH_BIAS_MAX * 4);
+    e->n_seq_bias = 0;            // (a failed copy leaves no half-written table in use)
+    HIP_OK(hipMemcpyAsync(e->d_sb_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(e->d_sb_tok.p, tok.data(), tok.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(e->d_sb_val.p, val.data(), val.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st));        // the host images above end with this call
+    e->n_seq_bias = n;
   });
 }
 

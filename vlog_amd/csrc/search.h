@@ -3,6 +3,8 @@
 
 #define SEARCH_SB 1024           // threads per logits row (logits_select_kernel)
 #define SEARCH_PER 52            // ids per thread: vocab <= SEARCH_SB * SEARCH_PER = 53248
+#define SEARCH_BIAS_MAX 1024     // sequence-bias table: entries
+#define SEARCH_BIAS_LEN 16       // ... and tokens per entry
 
 struct SearchParams {
   const float* logits;   // [rows][V] f32, row r belongs to hypothesis r
@@ -55,6 +57,14 @@ struct SearchParams {
   // length and the total length limit of the window in each hypothesis slot, [n_hyp], device memory
   const int* hyp_begin;
   const int* hyp_maxlen;
+  // sequence bias (search.hip header; n_bias 0: off, and launch_logits_select then runs the instantiations without
+  // it): entry j is tokens bias_tok[bias_off[j] .. bias_off[j + 1]) (1 .. SEARCH_BIAS_LEN ids inside the vocabulary)
+  // with bias bias_val[j]; the entries are sorted by their LAST token, entries with the same last token in the
+  // caller's order.  Device memory.
+  const int* bias_off;             // [n_bias + 1]
+  const int* bias_tok;
+  const float* bias_val;           // [n_bias], finite
+  int n_bias;                      // <= SEARCH_BIAS_MAX
 };
 
 struct BeamParams {

@@ -20,6 +20,15 @@
 //   no-repeat n-gram n: every id that would complete an n-gram already in that history is masked.
 // They live in their own instantiations (RULES): with both off the kernels launched are the ones without them.
 //
+// Sequence bias (BIAS; transformers' SequenceBiasLogitsProcessor over the same generated history): a table of
+// (token sequence s_j, bias b_j), set per engine by wm_set_sequence_bias.  Entry j is active when the last n_j - 1
+// generated tokens equal s_j[:-1] (n_j = 1: always), and every active entry adds b_j to the logit of s_j[-1].  The
+// bias comes after the repetition penalty and before every mask (a masked id stays masked), so it feeds the timestamp
+// forcing, the normaliser, the records and the beam candidates.  The engine stores the table sorted by the completing
+// id (stable, so entries that end in one id keep their order): the entries of an id are one contiguous run, found by
+// a binary search and summed in entry order, whatever the thread schedule.  A non-empty table selects the BIAS
+// instantiations (which carry RULES); an empty one launches exactly the kernels above.
+//
 // Ragged prompts (RAG): one wm_generate call may hold windows whose prompts differ in length and whose total length
 // limits differ.  The prompt length (p.sample_begin) and the limit (p.max_length) then come from per-hypothesis
 // tables in device memory (p.hyp_begin / p.hyp_maxlen, indexed like seq_len), which the host fills once (lockstep
@@ -87,10 +96,17 @@ __device__ float block_sum(float v, float* sh) {
 // layout (id t -> word t % SB, bit t / SB) are filled by the history scan that already finds the last timestamp:
 // s_seen marks the ids of the generated history, s_ban the ids an n-gram repeat would complete.  Each thread then
 // reads its own two words once: the ban word joins `rule`, the seen word rescales the register-resident row.
-template <int MODE, bool REC, bool RULES, bool RAG>
+// BIAS (with RULES): the sequence bias.  One thread per table entry compares the entry's prefix with the history tail
+// and writes its bias (0 when inactive) to s_bval and, when active, the completing id's bit to s_bias (s_seen layout).
+// A thread whose s_bias word is non-zero (rare) sums the id's run of entries and adds it to the register-resident row.
+template <int MODE, bool REC, bool RULES, bool RAG, bool BIAS = false>
 __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
+  static_assert(!BIAS || RULES, "the sequence bias lives in the RULES instantiations");
   __shared__ unsigned long long s_seen[RULES ? SB : 1];
   __shared__ unsigned long long s_ban[RULES ? SB : 1];
+  __shared__ unsigned long long s_bias[BIAS ? SB : 1];
+  __shared__ int s_bid[BIAS ? SEARCH_BIAS_MAX : 1];        // entry -> its completing id (ascending)
+  __shared__ float s_bval[BIAS ? SEARCH_BIAS_MAX : 1];     // entry -> its bias if active at this step, else 0
   __shared__ Cand sh_c[NW];
   __shared__ float sh_f[NW];
   __shared__ int s_info[4];
@@ -110,7 +126,22 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
     s_seen[tid] = 0;
     s_ban[tid] = 0;
   }
+  if (BIAS) s_bias[tid] = 0;
   __syncthreads();
+  if (BIAS) {
+    const int G = len - sample_begin;
+    for (int j = tid; j < p.n_bias; j += SB) {
+      const int o0 = p.bias_off[j], nj = p.bias_off[j + 1] - o0;
+      const int* sj = p.bias_tok + o0;
+      const int t = sj[nj - 1];
+      // the last nj - 1 generated tokens against s_j[:-1]: nj - 1 <= G keeps seq[len - m] inside the history
+      bool act = nj - 1 <= G;
+      for (int m = 1; m < nj && act; ++m) act = sj[nj - 1 - m] == seq[len - m];
+      s_bid[j] = t;
+      s_bval[j] = act ? p.bias_val[j] : 0.f;
+      if (act) atomicOr((unsigned*)s_bias + 2 * (t % SB) + ((t / SB) >> 5), 1u << ((t / SB) & 31));
+    }
+  }
   for (int i = sample_begin + tid; i < len; i += SB) {
     const int t = seq[i];
     if (t >= tb) atomicMax(&s_last_ts, i);
@@ -196,6 +227,27 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
 #pragma unroll
     for (int k = 0; k < PER; ++k)
       if ((seen >> k) & 1) xv[k] *= xv[k] < 0.f ? pen : inv_pen;
+  }
+  // the summed bias of id t: its run of entries starts at the lower bound of t in s_bid; inactive entries add 0
+  auto bias_of = [&](int t) -> float {
+    int lo = 0, hi = p.n_bias;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_bid[BIAS ? mid : 0] < t) lo = mid + 1; else hi = mid;
+    }
+    float add = 0.f;
+    for (; lo < p.n_bias && s_bid[BIAS ? lo : 0] == t; ++lo) add += s_bval[BIAS ? lo : 0];
+    return add;
+  };
+  if (BIAS) {
+    // (a loop over the set bits with an unrolled select: xv is never indexed dynamically, and the search stands once)
+    for (unsigned long long bw = s_bias[tid]; bw; bw &= bw - 1) {
+      const int kb = __builtin_ctzll(bw);
+      const float add = bias_of(tid + kb * SB);
+#pragma unroll
+      for (int k = 0; k < PER; ++k)
+        if (k == kb) xv[k] += add;
+    }
   }
   live = ~(sup | rule) & ((1ull << PER) - 1);
   // pass 1: per-segment max / argmax (and Gumbel keys for sampling, local top-k for beam)
@@ -450,6 +502,9 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
     if constexpr (RULES) {
       float xt = lg[tok];
       if ((s_seen[tok % SB] >> (tok / SB)) & 1) xt *= xt < 0.f ? p.rep_penalty : 1.0f / p.rep_penalty;
+      if constexpr (BIAS) {
+        if ((s_bias[tok % SB] >> (tok / SB)) & 1) xt += bias_of(tok);
+      }
       lp = xt - Z;
     } else {
       lp = lg[tok] - Z;
@@ -523,15 +578,24 @@ void launch_logits_select(const SearchParams& p, int n_rows, hipStream_t st) {
   const bool rec = p.tok_lp != nullptr && p.mode != 1;     // beam: beam_select_kernel keeps the records
   if (!(p.rep_penalty > 0.f) || p.no_repeat_ngram < 0)
     throw std::runtime_error("logits_select: repetition penalty must be > 0 and the n-gram size >= 0");
-  const bool rules = p.rep_penalty != 1.0f || p.no_repeat_ngram > 0;
+  if (p.n_bias < 0 || p.n_bias > SEARCH_BIAS_MAX || (p.n_bias > 0 && (!p.bias_off || !p.bias_tok || !p.bias_val)))
+    throw std::runtime_error("logits_select: bad sequence-bias table");
+  const bool bias = p.n_bias > 0;
+  const bool rules = bias || p.rep_penalty != 1.0f || p.no_repeat_ngram > 0;
   if ((p.hyp_begin != nullptr) != (p.hyp_maxlen != nullptr))
     throw std::runtime_error("logits_select: the per-hypothesis tables come as a pair");
   const bool rag = p.hyp_begin != nullptr;
   const dim3 g(n_rows), b(SB);
 #define SEL_LAUNCH(MODE, REC, RULES)                                                                      \
   do {                                                                                                    \
-    if (rag) hipLaunchKernelGGL((logits_select_kernel<MODE, REC, RULES, true>), g, b, 0, st, p);          \
-    else hipLaunchKernelGGL((logits_select_kernel<MODE, REC, RULES, false>), g, b, 0, st, p);             \
+    if (RULES && bias) {                                                                                  \
+      if (rag) hipLaunchKernelGGL((logits_select_kernel<MODE, REC, true, true, true>), g, b, 0, st, p);   \
+      else hipLaunchKernelGGL((logits_select_kernel<MODE, REC, true, false, true>), g, b, 0, st, p);      \
+    } else if (rag) {                                                                                     \
+      hipLaunchKernelGGL((logits_select_kernel<MODE, REC, RULES, true>), g, b, 0, st, p);                 \
+    } else {                                                                                              \
+      hipLaunchKernelGGL((logits_select_kernel<MODE, REC, RULES, false>), g, b, 0, st, p);                \
+    }                                                                                                     \
   } while (0)
   switch ((rules ? 6 : 0) + p.mode * 2 + (rec ? 1 : 0)) {
     case 0: SEL_LAUNCH(0, false, false); break;

@@ -361,13 +361,20 @@ class GpuEngine:
                  sot_index: Union[None, int, Sequence[int]] = None, check_every: int = 4, max_rows: int = 0,
                  compact: bool = False, record_logprobs: bool = False, stats: Optional[dict] = None,
                  repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
-                 prompt_lens: Optional[Sequence[int]] = None) -> Tuple[List[GenResult], int]:
+                 prompt_lens: Optional[Sequence[int]] = None,
+                 sequence_bias: Optional[Sequence[Tuple[Sequence[int], float]]] = None
+                 ) -> Tuple[List[GenResult], int]:
         """ctranslate2 Whisper.generate over windows in slots (wm_generate).  max_rows / compact: the row-set decode
         (greedy / one sampled hypothesis; windows refill finished rows in the given order, include/whisper_mi355.h);
         beam search with compact drops finished windows' hypotheses from the passes.
         record_logprobs: per-step log-prob records in each GenResult.  stats: filled with the decode's counters.
         repetition_penalty / no_repeat_ngram_size: CTranslate2's two logit rules over each hypothesis' generated tokens,
         applied on the device before every other rule (1.0 and 0: off; a negative value raises RuntimeError).
+        sequence_bias: a list of (token tuple, float) (wm_set_sequence_bias: an additive bias on the token that would
+        complete the sequence after the generated tokens, after the penalty and before every mask; scores and records
+        are those of the biased distribution).  The table is set for this call and cleared when it ends, so a shared
+        engine never keeps another caller's table; None and [] set none.  An invalid table raises RuntimeError naming
+        the entry.
         Ragged prompts (ABI 4): the prompts may differ in length (they are padded to the longest and the lengths passed
         on); sot_index=None then derives one index per prompt, and max_length may be one total length per window
         (prompt included).  prompt_lens: the prompts are rows of one length already and window w's prompt is the first
@@ -435,7 +442,13 @@ class GpuEngine:
             float(repetition_penalty), int(no_repeat_ngram_size),
             _i32p(h_lens) if ragged else None, _i32p(h_sots) if ragged else None, _i32p(h_mls) if ragged else None)
         with torch.cuda.device(self.device):
-            _capi.check(self.lib.wm_generate(self.h, C.byref(a), self.stream_ptr()), "wm_generate")
+            if sequence_bias:
+                self.set_sequence_bias(sequence_bias)
+            try:
+                _capi.check(self.lib.wm_generate(self.h, C.byref(a), self.stream_ptr()), "wm_generate")
+            finally:
+                if sequence_bias:
+                    self.set_sequence_bias(())
         res = []
         for w in range(W):
             n = int(lens[w])
@@ -448,6 +461,17 @@ class GpuEngine:
         if stats is not None:
             stats.update(passes=int(st64[0]), row_steps=int(st64[1]), refills=int(st64[2]), graph_captures=int(st64[3]))
         return res, int(steps[0])
+
+    def set_sequence_bias(self, table: Sequence[Tuple[Sequence[int], float]]) -> None:
+        """wm_set_sequence_bias: the engine's table for every later generate until it is replaced (empty: cleared)."""
+        seqs = [[int(t) for t in s] for s, _ in table]
+        off = np.zeros(len(seqs) + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.int64).astype(np.int32) if seqs else 0
+        toks = np.ascontiguousarray([t for s in seqs for t in s] or [0], dtype=np.int32)
+        bias = np.ascontiguousarray([float(b) for _, b in table] or [0.0], dtype=np.float32)
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.wm_set_sequence_bias(self.h, len(seqs), _i32p(off), _i32p(toks), _f32p(bias),
+                                                      self.stream_ptr()), "wm_set_sequence_bias")
 
     def forward(self, slots: Sequence[int], tokens: np.ndarray, last_only: bool = False,
                 align_heads: Sequence[Tuple[int, int]] = ()) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:

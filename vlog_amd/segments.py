@@ -5,6 +5,8 @@
       timestamp means "no speech after it" (seek advances a whole window), otherwise seek moves to the last
       timestamp (2 mel frames per timestamp step).
   build_prompt — `get_prompt`: previous text, hotwords, sot sequence and prefix into one decoder prompt.
+  build_sequence_bias, load_sequence_bias_file — the sequence-bias option: {phrase or token tuple: bias} into the
+      engine's table of (token tuple, bias) entries, and the VLOG_AMD_SEQUENCE_BIAS file.
   compression_ratio — len(utf8) / len(zlib(utf8)) (fallback trigger above 2.4).
   needs_fallback — the generate_with_fallback decision (compression ratio, avg logprob, silence exemption).
   avg_logprob — recovered from the CTranslate2 score: score * len**length_penalty / (len + 1).
@@ -14,7 +16,9 @@
 from __future__ import annotations
 
 import zlib
-from typing import Callable, List, Optional, Sequence, Tuple
+import json
+import math
+from typing import Callable, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -89,6 +93,67 @@ def build_prompt(encode: Callable[[str], List[int]], sot_sequence: Sequence[int]
             prompt.append(timestamp_begin)
         prompt.extend(pf)
     return prompt
+
+
+SEQUENCE_BIAS_MAX_ENTRIES = 1024        # the engine's limits (wm_set_sequence_bias)
+SEQUENCE_BIAS_MAX_TOKENS = 16
+
+
+def build_sequence_bias(encode: Callable[[str], List[int]], mapping: Mapping[Union[str, Tuple[int, ...]], float],
+                        n_vocab: int) -> List[Tuple[Tuple[int, ...], float]]:
+    """The `sequence_bias` option -> the engine's table [(token tuple, bias)], in the mapping's order.
+
+    A str key becomes two entries, the tokenisations of " " + text (the word inside a sentence) and of text (the word
+    at the start of a window), one entry when both are the same ids.  A tuple of ints is taken as it is.  Every entry
+    adds its bias to the logit of its LAST token when the generated tokens end in the ones before it (transformers'
+    SequenceBiasLogitsProcessor): only the completing token is biased, so to favour a multi-token name from its
+    first token, list its prefixes as keys of their own.  Raises ValueError naming the key on an empty tokenisation,
+    one of more than 16 tokens, an id outside [0, n_vocab), a non-finite bias, or more than 1024 entries."""
+    if not isinstance(mapping, Mapping):
+        raise ValueError("sequence_bias must be a mapping {phrase or token tuple: bias}")
+    table: List[Tuple[Tuple[int, ...], float]] = []
+    for key, bias in mapping.items():
+        try:
+            b = float(bias)
+        except (TypeError, ValueError):
+            raise ValueError(f"sequence_bias[{key!r}]: the bias must be a number, got {bias!r}") from None
+        if not math.isfinite(b) or abs(b) > float(np.finfo(np.float32).max):
+            raise ValueError(f"sequence_bias[{key!r}]: the bias must be finite (f32), got {bias!r}")
+        if isinstance(key, str):
+            seqs = [tuple(int(t) for t in encode(" " + key)), tuple(int(t) for t in encode(key))]
+            if seqs[0] == seqs[1]:
+                seqs.pop()
+        elif isinstance(key, tuple) and all(isinstance(t, (int, np.integer)) and not isinstance(t, bool) for t in key):
+            seqs = [tuple(int(t) for t in key)]
+        else:
+            raise ValueError(f"sequence_bias key {key!r}: a str or a tuple of token ids expected")
+        for seq in seqs:
+            if not 1 <= len(seq) <= SEQUENCE_BIAS_MAX_TOKENS:
+                raise ValueError(f"sequence_bias[{key!r}]: {len(seq)} tokens, 1 to {SEQUENCE_BIAS_MAX_TOKENS} expected")
+            if any(t < 0 or t >= n_vocab for t in seq):
+                raise ValueError(f"sequence_bias[{key!r}]: token id outside the vocabulary in {seq}")
+            table.append((seq, b))
+    if len(table) > SEQUENCE_BIAS_MAX_ENTRIES:
+        raise ValueError(f"sequence_bias: {len(table)} entries, at most {SEQUENCE_BIAS_MAX_ENTRIES}")
+    return table
+
+
+def load_sequence_bias_file(path: str) -> dict:
+    """The VLOG_AMD_SEQUENCE_BIAS file: one JSON object {"phrase": bias} -> {str: float}.  Raises ValueError naming the
+    file when it is missing, no JSON object, or holds a value that is no finite number."""
+    try:
+        with open(path, "r", encoding="utf-8") as f:
+            data = json.load(f)
+    except (OSError, ValueError) as ex:
+        raise ValueError(f"VLOG_AMD_SEQUENCE_BIAS={path!r}: {ex}") from None
+    if not isinstance(data, dict):
+        raise ValueError(f"VLOG_AMD_SEQUENCE_BIAS={path!r}: a JSON object {{\"phrase\": bias}} expected")
+    out = {}
+    for k, v in data.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"VLOG_AMD_SEQUENCE_BIAS={path!r}: the bias of {k!r} must be a finite number, got {v!r}")
+        out[k] = float(v)
+    return out
 
 
 def compression_ratio(text: str) -> float:

@@ -28,7 +28,7 @@ import logging
 import os
 import threading
 from dataclasses import asdict, dataclass, field
-from typing import BinaryIO, Iterable, List, Optional, Sequence, Tuple, Union
+from typing import BinaryIO, Iterable, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -108,6 +108,8 @@ class TranscriptionOptions:
     hallucination_silence_threshold: Optional[float]
     hotwords: Optional[str]
     section_frames: Optional[List[Tuple[int, int]]] = None     # transcribe(sections=N): the (start, end) chosen
+    sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None   # as passed (or the environment file's)
+    sequence_bias_table: Optional[List[Tuple[Tuple[int, ...], float]]] = None     # ... as the engine takes it
 
 
 @dataclass
@@ -212,6 +214,12 @@ class WhisperModel:
         vad_spec = vad_model if vad_model is not None else default_spec()
         self.vad_net = SileroVad.from_spec(self.engine, vad_spec) if vad_spec else None
         self._lock = threading.RLock()
+        # VLOG_AMD_SEQUENCE_BIAS=<JSON file {"phrase": bias}>: the sequence bias of every call that passes none (the
+        # unchanged worker's custom vocabulary); read and tokenised once here, so a bad file fails the construction
+        self._env_sequence_bias = None
+        if os.environ.get("VLOG_AMD_SEQUENCE_BIAS"):
+            self._env_sequence_bias = segs.load_sequence_bias_file(os.environ["VLOG_AMD_SEQUENCE_BIAS"])
+            segs.build_sequence_bias(self.tokenizer().encode, self._env_sequence_bias, self.dims.n_vocab)
         self.feature_size = self.dims.n_mels
         self.num_samples_per_token = HOP_LENGTH * INPUT_STRIDE
         self.frames_per_second = FRAMES_PER_SECOND
@@ -237,6 +245,17 @@ class WhisperModel:
 
     def tokenizer(self, task: Optional[str] = "transcribe", language: Optional[str] = None) -> Tokenizer:
         return Tokenizer(self.dims, task=task, language=language, tokenizer_json=self._tokenizer_json, seed=self._tok_seed)
+
+    def _sequence_bias(self, tokenizer: Tokenizer, sequence_bias):
+        """The `sequence_bias` argument of a transcribe call -> (the mapping in force, the engine's table or None).
+        None takes the VLOG_AMD_SEQUENCE_BIAS file's mapping when there is one; anything but a mapping (a per-file
+        list, say: the table is one per call, like the suppress list) raises ValueError."""
+        if sequence_bias is None:
+            sequence_bias = self._env_sequence_bias
+        if sequence_bias is None:
+            return None, None
+        table = segs.build_sequence_bias(tokenizer.encode, sequence_bias, self.dims.n_vocab)
+        return dict(sequence_bias), (table or None)
 
     # ------------------------------------------------------------------ features / encoder
     def _load_audio(self, src) -> np.ndarray:
@@ -322,8 +341,19 @@ class WhisperModel:
                    clip_timestamps: Union[str, List[float]] = "0", hallucination_silence_threshold: Optional[float] = None,
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
                    language_detection_segments: int = 1, sections: Optional[int] = None,
-                   sections_in_flight: Optional[int] = None):
-        """faster-whisper's `WhisperModel.transcribe`, plus two arguments of this engine:
+                   sections_in_flight: Optional[int] = None,
+                   sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None):
+        """faster-whisper's `WhisperModel.transcribe`, plus three arguments of this engine:
+
+        sequence_bias: {phrase or token tuple: bias}, deterministic custom-vocabulary boosts (bias > 0) and soft or
+        hard bans (bias < 0; -100 is a ban) applied on the device at every decode step of every decode form (beam
+        search, the fallback temperatures, sections=N; transformers' SequenceBiasLogitsProcessor over the window's
+        generated tokens, segments.build_sequence_bias).  A phrase stands for its tokenisations with and without a
+        leading space.  Only the token that COMPLETES an entry is biased, and only when the tokens before it were just
+        generated: to favour a multi-token name from its first token, list its prefixes as keys of their own.  The
+        bias is part of the distribution: avg_logprob, the fallback thresholds and the beam scores are those of the
+        biased distribution.  Default: the VLOG_AMD_SEQUENCE_BIAS file, else none.  The mapping in force is echoed in
+        info.transcription_options.sequence_bias.
 
         sections: cut the file at up to sections - 1 long silences into contiguous sections (seek_state.plan_sections:
         near the even split points, at a VAD chunk join with at least 0.5 s removed, or without VAD at the quietest
@@ -379,7 +409,7 @@ class WhisperModel:
                 word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
         if sections > 1 and not isinstance(audio, np.ndarray):
             audio = self._load_audio(audio)     # (the cuts without VAD are chosen on the samples)
         features, tokenizer, options, info, speech_chunks = self._prepare_file(
@@ -396,7 +426,7 @@ class WhisperModel:
             max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
             hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hotwords,
             language_detection_threshold=language_detection_threshold,
-            language_detection_segments=language_detection_segments)
+            language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
         bounds = self._plan_sections(audio, features, speech_chunks, sections) if sections > 1 else None
         if bounds is not None:
             options.section_frames = bounds
@@ -428,7 +458,7 @@ class WhisperModel:
                       prefix, suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp,
                       word_timestamps, prepend_punctuations, append_punctuations, multilingual, vad_filter,
                       vad_parameters, max_new_tokens, clip_timestamps, hallucination_silence_threshold, hotwords,
-                      language_detection_threshold, language_detection_segments):
+                      language_detection_threshold, language_detection_segments, sequence_bias=None):
         """What `transcribe` does for one file before its seek loop: load, VAD, log-mel, language, tokenizer, options.
         -> (features, tokenizer, options, info, speech_chunks)"""
         if not isinstance(audio, np.ndarray):
@@ -462,6 +492,7 @@ class WhisperModel:
             language_probability = 1.0
         tokenizer = self.tokenizer(task=task, language=language)
         temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
+        bias_map, bias_table = self._sequence_bias(tokenizer, sequence_bias)
         options = TranscriptionOptions(
             beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
             repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -474,7 +505,7 @@ class WhisperModel:
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
             append_punctuations=append_punctuations, multilingual=multilingual, max_new_tokens=max_new_tokens,
             clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
-            hotwords=hotwords)
+            hotwords=hotwords, sequence_bias=bias_map, sequence_bias_table=bias_table)
         info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
                                  duration_after_vad=duration_after_vad, all_language_probs=all_language_probs,
                                  transcription_options=options, vad_options=vad_opts)
@@ -499,7 +530,8 @@ class WhisperModel:
             suppress_blank=options.suppress_blank, max_initial_timestamp_index=mit,
             with_timestamps=not options.without_timestamps,
             sot_index=prompt.index(st.sot) if st.sot in prompt else -1, check_every=4,
-            repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size)
+            repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size,
+            sequence_bias=options.sequence_bias_table)
         r = res[0]
         return _GenOut(r.tokens, r.score, r.no_speech_prob)
 
@@ -587,7 +619,8 @@ class WhisperModel:
                         suppress_blank=opt0.suppress_blank, max_initial_timestamp_index=mit,
                         with_timestamps=not opt0.without_timestamps,
                         sot_index=[p.index(sot) if sot in p else -1 for p in prompts], check_every=4,
-                        repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size)
+                        repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size,
+                        sequence_bias=opt0.sequence_bias_table)
                     for i, r in zip(members, res):
                         out[i] = _GenOut(r.tokens, r.score, r.no_speech_prob)
                 return out
@@ -653,7 +686,8 @@ class WhisperModel:
                         chunk_length: Optional[int] = None, clip_timestamps: Union[str, List[float]] = "0",
                         hallucination_silence_threshold: Optional[float] = None, hotwords=None,
                         language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
-                        max_files: int = 16):
+                        max_files: int = 16,
+                        sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None):
         """`transcribe` for several files at once in the sequential (parity) mode -> [(list_of_segments, info)] in
         input order; each file gets what `transcribe(file, same arguments)` gives for it alone.
 
@@ -666,7 +700,8 @@ class WhisperModel:
         word timestamps are aligned per file against its own slot.  language / initial_prompt / hotwords / prefix take
         one value, or a list / tuple with one value per file (pass token ids of ONE initial prompt as a numpy array or
         repeat them per file).  Files of different languages share rounds (the prompt carries the language); files whose
-        suppress lists differ are decoded in separate generate calls of the round.
+        suppress lists differ are decoded in separate generate calls of the round.  sequence_bias (see `transcribe`) is
+        ONE mapping for all files, as the engine holds one table per generate call: a per-file list raises ValueError.
         max_files: files in flight.  Measured on one MI355X (large-v3 margin weights, the worker's call on 5-minute
         clips, tools/bench_worker_call.py --files, profiles/worker_call_many.jsonl): files in flight -> RTFx summed
         over the files / ms per decoder pass: 1 -> 133 / 2.10, 2 -> 240 / 2.31, 4 -> 365 / 3.03, 8 -> 593 / 3.64,
@@ -686,6 +721,8 @@ class WhisperModel:
         n = len(audios)
         if max_files < 1:
             raise ValueError("max_files must be >= 1")
+        if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
+            raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
 
         def per_file(v, name):
             if isinstance(v, (list, tuple)):
@@ -712,7 +749,7 @@ class WhisperModel:
                 word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
 
         files: dict = {}
         results: List[List[Segment]] = [[] for _ in range(n)]
@@ -733,7 +770,7 @@ class WhisperModel:
                 vad_parameters=vad_parameters, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
                 hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hot[f],
                 language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
             files[f] = [features, info, chunks]
             return SeekState(features.shape[1] - 1, tokenizer, options, self.max_length, self.frames_per_second)
 
@@ -1043,7 +1080,8 @@ class BatchedInferencePipeline:
                         max_initial_timestamp_index=mit, with_timestamps=not options.without_timestamps,
                         sot_index=prompt.index(st.sot), check_every=4, compact=self.compact,
                         repetition_penalty=options.repetition_penalty,
-                        no_repeat_ngram_size=options.no_repeat_ngram_size)
+                        no_repeat_ngram_size=options.no_repeat_ngram_size,
+                        sequence_bias=options.sequence_bias_table)
                     still = []
                     for i, r in zip(pending, res):
                         alp = segs.avg_logprob(r.score, len(r.tokens), options.length_penalty)
@@ -1109,7 +1147,9 @@ class BatchedInferencePipeline:
                    max_new_tokens: Optional[int] = None, chunk_length: Optional[int] = None, clip_timestamps=None,
                    hallucination_silence_threshold: Optional[float] = None, batch_size: int = 16,
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
-                   language_detection_segments: int = 1):
+                   language_detection_segments: int = 1,
+                   sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None):
+        """sequence_bias: as WhisperModel.transcribe (one table for every window of the file)."""
         for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
             if val != default:
@@ -1127,7 +1167,8 @@ class BatchedInferencePipeline:
             initial_prompt=initial_prompt, suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
             without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-            append_punctuations=append_punctuations, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps)
+            append_punctuations=append_punctuations, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
+            sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias))
         windows = prep["windows"]
         offsets = [s * HOP_LENGTH / SAMPLE_RATE for s, _ in windows]
         results = self.decode_windows(prep["features"], windows, offsets, tokenizer, options, last_speech={})
@@ -1143,10 +1184,14 @@ class BatchedInferencePipeline:
         into the same batches: the files' log-mel matrices are concatenated along time (each normalised with
         its own global max, as faster-whisper does per file) and every window keeps its file's time offsets.
         Returns [(segments, info)] per file, in input order; each file's result is what `transcribe` gives for
-        it alone (same windows, prompts and options)."""
+        it alone (same windows, prompts and options).  sequence_bias (in **kw, see WhisperModel.transcribe) is one
+        mapping for all files; a per-file list raises ValueError."""
         n = len(audios)
         if kw.pop("prefix", None) is not None:
             raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
+        sequence_bias = kw.pop("sequence_bias", None)
+        if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
+            raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
         langs = list(language) if isinstance(language, (list, tuple)) else [language] * n
         if len(langs) != n:
             raise ValueError("one language per file")
@@ -1157,7 +1202,7 @@ class BatchedInferencePipeline:
         for lang in sorted({p["language"] for p in preps}):
             files = [i for i, p in enumerate(preps) if p["language"] == lang]
             tokenizer = self.model.tokenizer(task=task, language=lang)
-            options = self._options(tokenizer, **kw)
+            options = self._options(tokenizer, sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias), **kw)
             feats = torch.cat([preps[i]["features"] for i in files], dim=1) if len(files) > 1 else preps[files[0]]["features"]
             windows, offsets, fids, bases = [], [], [], {}
             base = 0
@@ -1225,7 +1270,9 @@ class BatchedInferencePipeline:
                  max_initial_timestamp: float = 1.0, word_timestamps: bool = False,
                  prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
                  max_new_tokens: Optional[int] = None, clip_timestamps=None, repetition_penalty: float = 1,
-                 no_repeat_ngram_size: int = 0, hotwords: Optional[str] = None) -> TranscriptionOptions:
+                 no_repeat_ngram_size: int = 0, hotwords: Optional[str] = None,
+                 sequence_bias=(None, None)) -> TranscriptionOptions:
+        """sequence_bias: (the mapping in force, the engine's table), WhisperModel._sequence_bias' pair"""
         temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
         return TranscriptionOptions(
             beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
@@ -1238,7 +1285,8 @@ class BatchedInferencePipeline:
             without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
             append_punctuations=append_punctuations, multilingual=False, max_new_tokens=max_new_tokens,
-            clip_timestamps=clip_timestamps or "0", hallucination_silence_threshold=None, hotwords=hotwords)
+            clip_timestamps=clip_timestamps or "0", hallucination_silence_threshold=None, hotwords=hotwords,
+            sequence_bias=sequence_bias[0], sequence_bias_table=sequence_bias[1])
 
     @staticmethod
     def _info(prep: dict, options: TranscriptionOptions) -> TranscriptionInfo:
