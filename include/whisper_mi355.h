@@ -166,7 +166,8 @@ int wm_cross_kv(wm_engine* e, const void* d_enc, int32_t B, int32_t slot0, void*
  * its no-speech probability is read at (h_sot_indices) and its total length limit (h_max_lengths), so windows
  * whose previous-text prompts differ in length (faster-whisper's condition_on_previous_text, one file per window)
  * decode in the same passes.  Each window's result is what a call with that window alone computes, to the f32
- * rounding of the pass's GEMM / attention routes (which follow the pass's row count). */
+ * rounding of the pass's GEMM / attention routes (which follow the pass's row count).  (Sampling: with the one
+ * `seed` of this struct a window's draws follow its place in the call; wm_generate_seeded takes a seed per window.) */
 typedef struct wm_generate_args {
   int32_t n_windows;
   const int32_t* h_slots;        /* [n_windows] cross-KV slot of each window */
@@ -254,6 +255,23 @@ typedef struct wm_generate_args {
 /* Failure contract: a NaN / inf logits row or a row whose rules allow no token, detected on the device, fails the
  * call (-1, wm_last_error names the window and step) instead of emitting a token. */
 int wm_generate(wm_engine* e, const wm_generate_args* a, void* stream);
+
+/* wm_generate with one sampling seed per window (the sequential mode's fallback ladder decoded by levels: the windows
+ * of several files or sections that failed temperature i re-decode together, each with its own file's seed
+ * window + i).  h_seeds == NULL, or a->temperature <= 0: exactly wm_generate(e, a, stream), the same kernels and
+ * the same bits.  Otherwise hypothesis j (0 <= j < num_hypotheses) of window w draws its Gumbel noise at its own
+ * decode step s and token i from (h_seeds[w], j, s, i) and a->seed is not read: the noise depends on the window's
+ * seed and the hypothesis' index inside its window, never on the window's place in the call.  The result of window w
+ * is therefore what a call with that window alone and seed = h_seeds[w] computes, to the f32 rounding of the pass's
+ * GEMM / attention routes (the guarantee ragged prompts give).  Every form that samples takes the seeds: the lockstep
+ * decode with any num_hypotheses, and the row-set forms (num_hypotheses 1 with max_rows below the windows, or
+ * compact), whose key (seed, w) becomes (h_seeds[w], 0).  The seeds live in per-hypothesis device tables filled once
+ * per call (row-set: when a slot takes a window), so no launch is added per step and captured step graphs stay valid;
+ * only the sampling selection has instantiations that read them.  Any u64 is a valid seed; validation, the failure
+ * contract, h_steps and h_stats are wm_generate's.  (Added without an ABI bump: a new entry point, wm_generate_args
+ * unchanged.) */
+int wm_generate_seeded(wm_engine* e, const wm_generate_args* a, const uint64_t* h_seeds /* [n_windows] or NULL */,
+                       void* stream);
 
 /* Sequence bias: the third rule over each hypothesis' GENERATED tokens (transformers' SequenceBiasLogitsProcessor):
  * custom-vocabulary boosts and soft or hard bans.  The table has n entries; entry j is the token sequence

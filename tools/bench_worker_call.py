@@ -23,6 +23,13 @@ time inside engine.generate over its pass count); N = 1 is `transcribe` on one f
 transcribe(sections=N) (the file's sections decoded in lockstep); one JSON line per N with the sections the plan gave,
 the wall times of --repeats calls (from the call to the VTT string), the RTFx of their median, and the decoder-pass
 figures of --files.  N = 0 calls transcribe without the argument, so the same file measures a tree from before it.
+
+--lockstep-fallback 0 | 1 | 0,1 (with --sections or --files): pass lockstep_fallback to the call (the fallback
+temperatures of a lockstep round decoded alone, or by levels in one seeded generate per temperature).  "0,1" times both
+at every point, alternated call by call inside the same process (--sections: --repeats calls of each), one JSON line per
+flag.  Every line then also splits engine.generate's counters (wm_generate h_stats, per call) into the first passes
+(temperature 0) and the fallback passes (temperature > 0): calls, decoder passes, rows per pass, ms per pass.  Without
+the option the argument is not passed at all, so the same file measures a tree from before it.
 """
 import argparse
 import json
@@ -58,7 +65,7 @@ def worker_call(model, wav, temperature=None):
 
 def time_generate(eng):
     """Wraps eng.generate -> the dict that accumulates its wall seconds, decoder passes, row steps and calls."""
-    acc = {"s": 0.0, "passes": 0, "rows": 0, "calls": 0}
+    acc = dict(ACC_ZERO)
     inner = eng.generate
 
     def timed_generate(*a, **kw):
@@ -66,14 +73,45 @@ def time_generate(eng):
         kw["stats"] = st
         t = time.perf_counter()
         r = inner(*a, **kw)
-        acc["s"] += time.perf_counter() - t
+        dt = time.perf_counter() - t
+        acc["s"] += dt
         acc["passes"] += st["passes"]
         acc["rows"] += st["row_steps"]
         acc["calls"] += 1
+        if kw.get("temperature", 0.0) > 0:      # the fallback ladder's share (a sampled decode)
+            acc["fb_s"] += dt
+            acc["fb_passes"] += st["passes"]
+            acc["fb_rows"] += st["row_steps"]
+            acc["fb_calls"] += 1
         return r
 
     eng.generate = timed_generate
     return acc
+
+
+ACC_ZERO = {"s": 0.0, "passes": 0, "rows": 0, "calls": 0, "fb_s": 0.0, "fb_passes": 0, "fb_rows": 0, "fb_calls": 0}
+
+
+def split_stats(acc, per=1):
+    """the first-pass / fallback split of time_generate's counters, per call of the measured function"""
+    first = {k: acc[k] - acc["fb_" + k] for k in ("s", "passes", "rows", "calls")}
+    out = {}
+    for name, d in (("first", first), ("fallback", {k: acc["fb_" + k] for k in ("s", "passes", "rows", "calls")})):
+        out[name] = {"generate_calls": d["calls"] // per, "decoder_passes": d["passes"] // per,
+                     "rows_per_pass": round(d["rows"] / max(d["passes"], 1), 2),
+                     "ms_per_decoder_pass": round(1e3 * d["s"] / max(d["passes"], 1), 4),
+                     "generate_s": round(d["s"] / per, 3)}
+    return out
+
+
+def fallback_flags(args):
+    """--lockstep-fallback -> the flags to time at every point ([None]: the argument is not passed)"""
+    if args.lockstep_fallback is None:
+        return [None]
+    flags = [int(v) for v in args.lockstep_fallback.split(",")]
+    if not flags or any(v not in (0, 1) for v in flags):
+        raise SystemExit("--lockstep-fallback takes 0, 1 or 0,1")
+    return flags
 
 
 def sectioned(model, args, spec, tmp):
@@ -84,10 +122,14 @@ def sectioned(model, args, spec, tmp):
     audio_s = n_win * 30.0
     acc = time_generate(model.engine)
 
-    def call(n):
+    flags = fallback_flags(args)
+
+    def call(n, flag=None):
         kw = dict(language=None, task="transcribe", beam_size=5, vad_filter=True)
         if args.temperature is not None:
             kw["temperature"] = args.temperature
+        if flag is not None:
+            kw["lockstep_fallback"] = bool(flag)
         if n > 0:
             kw["sections"] = n
             if args.sections_in_flight is not None:
@@ -96,27 +138,44 @@ def sectioned(model, args, spec, tmp):
         segments, info = model.transcribe(path, **kw)
         segs = [{"start": s.start, "end": s.end, "text": s.text} for s in segments]
         generate_webvtt(segs)
-        return time.perf_counter() - t, info, len(segs)
+        dt = time.perf_counter() - t
+        print(f"sections={n} lockstep_fallback={flag}: {dt:.3f} s", file=sys.stderr, flush=True)    # progress
+        return dt, info, len(segs)
 
     call(0)                                                        # warm-up (allocations, kernels)
     for n in counts:
-        call(n)                                                    # (the slots and rows of this point)
-        acc.update(s=0.0, passes=0, rows=0, calls=0)
-        walls = []
+        for flag in flags:
+            call(n, flag)                                          # (the slots and rows of this point)
+        # the flags alternate call by call, so drift of the box lands on both; counters are kept per flag
+        accs = {flag: dict(ACC_ZERO) for flag in flags}
+        walls = {flag: [] for flag in flags}
+        last = {}
         for _ in range(args.repeats):
-            dt, info, nseg = call(n)
-            walls.append(dt)
-        bounds = getattr(info.transcription_options, "section_frames", None)
-        med = float(np.median(walls))
-        print(json.dumps({"model": args.model, "weights": spec, "sections": n if n > 0 else None,
-                          "sections_planned": len(bounds) if bounds else 1,
-                          "sections_in_flight": args.sections_in_flight, "audio_s": audio_s,
-                          "duration_after_vad": round(info.duration_after_vad, 2),
-                          "wall_s": [round(w, 3) for w in walls], "rtfx": round(audio_s / med, 2),
-                          "rtfx_runs": [round(audio_s / w, 2) for w in walls], "segments": nseg,
-                          "generate_calls": acc["calls"] // args.repeats, "decoder_passes": acc["passes"] // args.repeats,
-                          "ms_per_decoder_pass": round(1e3 * acc["s"] / max(acc["passes"], 1), 4),
-                          "rows_per_pass": round(acc["rows"] / max(acc["passes"], 1), 2)}), flush=True)
+            for flag in flags:
+                acc.update(ACC_ZERO)
+                dt, info, nseg = call(n, flag)
+                walls[flag].append(dt)
+                last[flag] = (info, nseg)
+                for k in ACC_ZERO:
+                    accs[flag][k] += acc[k]
+        for flag in flags:
+            info, nseg = last[flag]
+            a = accs[flag]
+            bounds = getattr(info.transcription_options, "section_frames", None)
+            med = float(np.median(walls[flag]))
+            line = {"model": args.model, "weights": spec, "sections": n if n > 0 else None,
+                    "sections_planned": len(bounds) if bounds else 1,
+                    "sections_in_flight": args.sections_in_flight, "audio_s": audio_s,
+                    "duration_after_vad": round(info.duration_after_vad, 2),
+                    "wall_s": [round(w, 3) for w in walls[flag]], "rtfx": round(audio_s / med, 2),
+                    "rtfx_runs": [round(audio_s / w, 2) for w in walls[flag]], "segments": nseg,
+                    "generate_calls": a["calls"] // args.repeats, "decoder_passes": a["passes"] // args.repeats,
+                    "ms_per_decoder_pass": round(1e3 * a["s"] / max(a["passes"], 1), 4),
+                    "rows_per_pass": round(a["rows"] / max(a["passes"], 1), 2)}
+            if flag is not None:
+                line["lockstep_fallback"] = flag
+                line.update(split_stats(a, args.repeats))
+            print(json.dumps(line), flush=True)
 
 
 def many_files(model, args, spec, tmp):
@@ -134,18 +193,24 @@ def many_files(model, args, spec, tmp):
         kw["temperature"] = args.temperature
     list(model.transcribe(paths[0], **kw)[0])                      # warm-up
     for n in counts:
-        acc.update(s=0.0, passes=0, rows=0, calls=0)
-        t = time.perf_counter()
-        if n == 1:
-            nseg = len(list(model.transcribe(paths[0], **kw)[0]))
-        else:
-            nseg = sum(len(s) for s, _ in model.transcribe_many(paths[:n], max_files=n, **kw))
-        dt = time.perf_counter() - t
-        print(json.dumps({"model": args.model, "weights": spec, "files_in_flight": n, "call": "transcribe" if n == 1 else
-                          "transcribe_many", "audio_s_per_file": audio_s, "wall_s": round(dt, 3),
-                          "rtfx_sum": round(n * audio_s / dt, 2), "segments": nseg, "generate_calls": acc["calls"],
-                          "decoder_passes": acc["passes"], "ms_per_decoder_pass": round(1e3 * acc["s"] / max(acc["passes"], 1), 4),
-                          "rows_per_pass": round(acc["rows"] / max(acc["passes"], 1), 2)}), flush=True)
+        for flag in fallback_flags(args):
+            fkw = dict(kw) if flag is None else dict(kw, lockstep_fallback=bool(flag))
+            acc.update(ACC_ZERO)
+            t = time.perf_counter()
+            if n == 1:
+                nseg = len(list(model.transcribe(paths[0], **fkw)[0]))
+            else:
+                nseg = sum(len(s) for s, _ in model.transcribe_many(paths[:n], max_files=n, **fkw))
+            dt = time.perf_counter() - t
+            line = {"model": args.model, "weights": spec, "files_in_flight": n, "call": "transcribe" if n == 1 else
+                    "transcribe_many", "audio_s_per_file": audio_s, "wall_s": round(dt, 3),
+                    "rtfx_sum": round(n * audio_s / dt, 2), "segments": nseg, "generate_calls": acc["calls"],
+                    "decoder_passes": acc["passes"], "ms_per_decoder_pass": round(1e3 * acc["s"] / max(acc["passes"], 1), 4),
+                    "rows_per_pass": round(acc["rows"] / max(acc["passes"], 1), 2)}
+            if flag is not None:
+                line["lockstep_fallback"] = flag
+                line.update(split_stats(acc))
+            print(json.dumps(line), flush=True)
 
 
 def main():
@@ -168,6 +233,9 @@ def main():
     ap.add_argument("--sections-in-flight", type=int, default=None,
                     help="sections decoded per round (default: all; 1 = one after another, the A/B baseline)")
     ap.add_argument("--repeats", type=int, default=3, help="timed calls per --sections point")
+    ap.add_argument("--lockstep-fallback", default=None,
+                    help="0, 1 or 0,1: the lockstep_fallback argument at every --sections / --files point (module "
+                         "docstring); default: the argument is not passed")
     args = ap.parse_args()
     spec = f"synthetic:{args.model}:0" + ("" if args.random_weights else ":margin")
     model = WhisperModel(spec, device="cpu", compute_type="int8", eot_after=110)

@@ -23,6 +23,7 @@ SYMBOLS = (
     "wm_dtw_open", "wm_align_open_batch",
     "wm_cross_kv_fp8_quantize",
     "wm_set_sequence_bias",
+    "wm_generate_seeded",
 )
 
 
@@ -81,6 +82,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "wm_reserve": (C.c_int, [vp, i32, i32, vp]),
         "wm_cross_kv": (C.c_int, [vp, vp, i32, i32, vp]),
         "wm_generate": (C.c_int, [vp, C.POINTER(GenerateArgsC), vp]),
+        "wm_generate_seeded": (C.c_int, [vp, C.POINTER(GenerateArgsC), C.POINTER(C.c_uint64), vp]),
         "wm_set_sequence_bias": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float), vp]),
         "wm_forward": (C.c_int, [vp, i32, C.POINTER(i32), i32, C.POINTER(i32), vp, i32, C.POINTER(i32), i32, vp, vp]),
         "wm_frame_energy": (C.c_int, [vp, vp, i64, i32, vp, vp]),

@@ -174,6 +174,10 @@ struct wm_engine {
   // the event upload (pass rows, row set, logit rows, starts)
   DevBuf d_win_prompt, d_win_slot, d_hyp_out, d_res_tok, d_res_len, d_res_cum, d_res_ns, d_res_lp, d_res_lp_o, d_ev;
   DevBuf d_hyp_begin, d_hyp_maxlen, d_win_len, d_win_maxlen;   // ragged prompts (search.h hyp_begin / hyp_maxlen)
+  // per-window seeds (wm_generate_seeded; search.h hyp_seed / hyp_key): the running call's host seeds [n_windows]
+  // (nullptr outside such a call) and the device tables
+  const uint64_t* call_seeds = nullptr;
+  DevBuf d_hyp_seed, d_hyp_key, d_win_seed;
   std::vector<int> h_ev;     // host image of d_ev (kept alive until the next poll syncs the stream)
   // sequence-bias table (wm_set_sequence_bias; search.h bias_*): allocated once at the limits' size, so a captured
   // step graph's pointers stay valid whatever table follows
@@ -1404,6 +1408,18 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
     HIP_OK(hipMemcpyAsync(e->d_hyp_begin.p, seq_len.data(), NH * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(e->d_hyp_maxlen.p, hyp_ml.data(), NH * 4, hipMemcpyHostToDevice, st));
   }
+  // per-window seeds (wm_generate_seeded): hypothesis h = w * per + j draws as (seed of w, j); filled once, here
+  const bool seeded = sampling && e->call_seeds != nullptr;
+  std::vector<unsigned long long> hyp_seed;
+  std::vector<int> hyp_key;
+  if (seeded) {
+    hyp_seed.resize(NH); hyp_key.resize(NH);
+    for (int h = 0; h < NH; ++h) { hyp_seed[h] = e->call_seeds[h / per]; hyp_key[h] = h % per; }
+    e->d_hyp_seed.ensure((size_t)NH * 8);
+    e->d_hyp_key.ensure((size_t)NH * 4);
+    HIP_OK(hipMemcpyAsync(e->d_hyp_seed.p, hyp_seed.data(), (size_t)NH * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(e->d_hyp_key.p, hyp_key.data(), (size_t)NH * 4, hipMemcpyHostToDevice, st));
+  }
   HIP_OK(hipMemcpyAsync(e->d_tokens.p, tokens.data(), tokens.size() * 4, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(e->d_lin.p, lin.data(), lin.size() * 4, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(e->d_seq_len.p, seq_len.data(), NH * 4, hipMemcpyHostToDevice, st));
@@ -1516,6 +1532,7 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
   SearchParams sp = search_params(e, a, logits, P);
   sp.mode = beam ? 1 : (sampling ? 2 : 0); sp.topk = beam ? a->beam_size + 1 : 1;
   if (rag) { sp.hyp_begin = e->d_hyp_begin.as<int>(); sp.hyp_maxlen = e->d_hyp_maxlen.as<int>(); }
+  if (seeded) { sp.hyp_seed = e->d_hyp_seed.as<unsigned long long>(); sp.hyp_key = e->d_hyp_key.as<int>(); }
   if (rec) {
     sp.tok_lp = e->d_tok_lp.as<float>();
     if (!beam) sp.tok_lp_other = e->d_tok_lp_o.as<float>();
@@ -1708,6 +1725,18 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
   sp.hyp_out = e->d_hyp_out.as<int>();
   sp.res_tok = e->d_res_tok.as<int>(); sp.res_len = e->d_res_len.as<int>(); sp.res_cum = e->d_res_cum.as<float>();
   if (rag) upload_window_tables(e, wa, R, &sp, nullptr, st);
+  // per-window seeds (wm_generate_seeded): the per-window table goes up once, hyp_start copies a window's seed into
+  // its slot's row of the selection tables (rows no window has taken yet stay defined, as the ragged tables')
+  const bool seeded = sp.mode == 2 && e->call_seeds != nullptr;
+  if (seeded) {
+    e->d_win_seed.ensure((size_t)W * 8);
+    e->d_hyp_seed.ensure((size_t)R * 8);
+    e->d_hyp_key.ensure((size_t)R * 4);
+    HIP_OK(hipMemcpyAsync(e->d_win_seed.p, e->call_seeds, (size_t)W * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(e->d_hyp_seed.p, 0, (size_t)R * 8, st));
+    HIP_OK(hipMemsetAsync(e->d_hyp_key.p, 0, (size_t)R * 4, st));
+    sp.hyp_seed = e->d_hyp_seed.as<unsigned long long>(); sp.hyp_key = e->d_hyp_key.as<int>();
+  }
   if (rec) {
     sp.tok_lp = e->d_tok_lp.as<float>(); sp.tok_lp_other = e->d_tok_lp_o.as<float>();
     sp.res_lp = e->d_res_lp.as<float>(); sp.res_lp_other = e->d_res_lp_o.as<float>();
@@ -1763,7 +1792,9 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
                      e->d_seq_len.as<int>(), e->d_done.as<int>(), e->d_cum.as<float>(), e->d_hyp_slot.as<int>(),
                      e->d_hyp_out.as<int>(), s, rag ? e->d_win_len.as<int>() : nullptr,
                      rag ? e->d_win_maxlen.as<int>() : nullptr, rag ? e->d_hyp_begin.as<int>() : nullptr,
-                     rag ? e->d_hyp_maxlen.as<int>() : nullptr);
+                     rag ? e->d_hyp_maxlen.as<int>() : nullptr,
+                     seeded ? e->d_win_seed.as<unsigned long long>() : nullptr,
+                     seeded ? e->d_hyp_seed.as<unsigned long long>() : nullptr, seeded ? e->d_hyp_key.as<int>() : nullptr);
     HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, d.rh, (size_t)nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_OK(hipMemcpyAsync(counters, d.n_live, 4, hipMemcpyDeviceToDevice, s));
     decoder_pass(e, np, d.ptok, d.ppos, d.phyp, e->d_done.as<int>(), nullptr, d.lr, nr + nsot, logits, nullptr, 0, nullptr, 1,
@@ -2623,7 +2654,7 @@ void wm_destroy(wm_engine* e) {
                     &e->a_pj, &e->a_plen, &e->a_meta, &e->a_enc, &e->a_kv, &e->d_tok_lp, &e->d_tok_lp_o, &e->d_fin_lp, &e->d_win_prompt,
                     &e->d_win_slot, &e->d_hyp_out, &e->d_res_tok, &e->d_res_len, &e->d_res_cum, &e->d_res_ns, &e->d_res_lp,
                     &e->d_res_lp_o, &e->d_ev, &e->d_hyp_begin, &e->d_hyp_maxlen, &e->d_win_len, &e->d_win_maxlen,
-                    &e->d_sb_off, &e->d_sb_tok, &e->d_sb_val})
+                    &e->d_sb_off, &e->d_sb_tok, &e->d_sb_val, &e->d_hyp_seed, &e->d_hyp_key, &e->d_win_seed})
     b->release();
   for (auto& kv : e->rs_taps) kv.second.pp.release();
   if (e->st2) (void)hipStreamDestroy(e->st2);
@@ -2777,6 +2808,18 @@ int wm_cross_kv(wm_engine* e, const void* d_enc, int32_t B, int32_t slot0, void*
 int wm_generate(wm_engine* e, const wm_generate_args* a, void* stream) {
   return guarded(e, [&] {
     require_weights(e);
+    generate(e, a, (hipStream_t)stream);
+  });
+}
+
+int wm_generate_seeded(wm_engine* e, const wm_generate_args* a, const uint64_t* h_seeds, void* stream) {
+  return guarded(e, [&] {
+    require_weights(e);
+    struct SeedScope {                    // the seeds belong to this call alone, exceptions included
+      wm_engine* e;
+      SeedScope(wm_engine* e_, const uint64_t* s) : e(e_) { e->call_seeds = s; }
+      ~SeedScope() { e->call_seeds = nullptr; }
+    } scope(e, a->temperature > 0.f ? h_seeds : nullptr);
     generate(e, a, (hipStream_t)stream);
   });
 }

@@ -65,6 +65,12 @@ struct SearchParams {
   const int* bias_tok;
   const float* bias_val;           // [n_bias], finite
   int n_bias;                      // <= SEARCH_BIAS_MAX
+  // per-window seeds (sampling only; both or neither; nullptr: `seed` and the call-wide hypothesis index hold):
+  // the hypothesis in slot h draws gumbel(hyp_seed[h], hyp_key[h], step, i), hyp_key its index among its own
+  // window's hypotheses, so a window's draws do not depend on its place in the call.  [n_hyp], device memory,
+  // filled like hyp_begin / hyp_maxlen; launch_logits_select then runs the SEED instantiations of mode 2.
+  const unsigned long long* hyp_seed;
+  const int* hyp_key;
 };
 
 struct BeamParams {
@@ -88,11 +94,13 @@ struct BeamParams {
 // Row-set decode bookkeeping (engine.cpp generate_rows).  Start hypotheses: slot hs[i] takes window ws[i] (prompt
 // win_prompt[ws[i]][0..P) into tokens, seq_len P, live, cum 0, its cross slot and output id).  Ragged prompts
 // (win_len != nullptr): P is the row stride of win_prompt, window w's prompt is its first win_len[w] tokens, and the
-// slot's rows of the selection tables become hyp_begin[h] = win_len[w], hyp_maxlen[h] = win_maxlen[w].
+// slot's rows of the selection tables become hyp_begin[h] = win_len[w], hyp_maxlen[h] = win_maxlen[w].  Per-window
+// seeds (win_seed != nullptr): hyp_seed[h] = win_seed[w], hyp_key[h] = 0 (one hypothesis per window).
 void launch_hyp_start(int n, const int* hs, const int* ws, const int* win_prompt, int P, const int* win_slot, int n_ctx,
                       int* tokens, int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out, hipStream_t st,
                       const int* win_len = nullptr, const int* win_maxlen = nullptr, int* hyp_begin = nullptr,
-                      int* hyp_maxlen = nullptr);
+                      int* hyp_maxlen = nullptr, const unsigned long long* win_seed = nullptr,
+                      unsigned long long* hyp_seed = nullptr, int* hyp_key = nullptr);
 // Pass rows whose token / position live on the device: row i with src[i] >= 0 takes (row_tok, row_pos)[src[i]].
 void launch_rows_fill(int n, const int* src, int* tok, int* pos, const int* row_tok, const int* row_pos, hipStream_t st);
 void launch_beam_start(int n, const int* gs, const int* ws, int K, const int* win_prompt, int P, const int* win_slot,

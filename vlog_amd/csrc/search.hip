@@ -35,6 +35,13 @@
 // decode) or hyp_start / beam_start fill when a slot takes a window (row-set decodes): kernel arguments never change,
 // so captured step graphs stay valid across refills.  RAG is a template parameter of both select kernels: a call
 // without the tables launches the same instantiations as before, unchanged.
+//
+// Per-window seeds (SEED): the Gumbel noise of a sampled call is keyed on (p.seed, global hypothesis row), so a
+// window's draws depend on its place in the call.  With p.hyp_seed / p.hyp_key (per-hypothesis device tables, filled
+// where hyp_begin / hyp_maxlen are) hypothesis h draws gumbel(hyp_seed[h], hyp_key[h], step, i): its window's own
+// seed and its index among that window's hypotheses, which is what a call with the window alone and that seed draws.
+// SEED is a template parameter of the MODE 2 instantiations only; without the tables a call launches what it
+// launched before.
 #include "search.h"
 #include <stdexcept>
 #include <string>
@@ -99,9 +106,12 @@ __device__ float block_sum(float v, float* sh) {
 // BIAS (with RULES): the sequence bias.  One thread per table entry compares the entry's prefix with the history tail
 // and writes its bias (0 when inactive) to s_bval and, when active, the completing id's bit to s_bias (s_seen layout).
 // A thread whose s_bias word is non-zero (rare) sums the id's run of entries and adds it to the register-resident row.
-template <int MODE, bool REC, bool RULES, bool RAG, bool BIAS = false>
+// SEED (MODE 2): the noise key comes from p.hyp_seed / p.hyp_key (header comment); h is block-uniform, so both are
+// read once per block.
+template <int MODE, bool REC, bool RULES, bool RAG, bool BIAS = false, bool SEED = false>
 __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
   static_assert(!BIAS || RULES, "the sequence bias lives in the RULES instantiations");
+  static_assert(!SEED || MODE == 2, "per-window seeds belong to sampling");
   __shared__ unsigned long long s_seen[RULES ? SB : 1];
   __shared__ unsigned long long s_ban[RULES ? SB : 1];
   __shared__ unsigned long long s_bias[BIAS ? SB : 1];
@@ -256,7 +266,9 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
   const int K = MODE == 1 ? p.topk : 0;
   // Gumbel noise keyed on the WINDOW's hypothesis id, not the slot: the row-set decode reuses slots, and a window's
   // draws must not depend on which slot it got (hyp_out[h] = w there, one hypothesis per window; h = w*nh + j else)
-  const int gkey = MODE == 2 && p.hyp_out ? p.hyp_out[h] : h;
+  // SEED: the window's own seed and the hypothesis' index inside its window, whatever slot or place it has
+  const int gkey = SEED ? p.hyp_key[h] : (MODE == 2 && p.hyp_out ? p.hyp_out[h] : h);
+  const unsigned long long gseed = SEED ? p.hyp_seed[h] : p.seed;
   // (explicit branches, not a reference chosen per element: a `Cand& m = is_ts ? ms : mt` put both in scratch;
   // a select-only form of this pass spilled)
 #pragma unroll
@@ -273,7 +285,7 @@ __global__ __launch_bounds__(SB) void logits_select_kernel(SearchParams p) {
     if (MODE == 2) {
       // the decode step of this hypothesis = tokens it has sampled so far (equal to the host's step counter
       // for every live hypothesis; read from the device so a captured step graph replays unchanged)
-      const float key = x * p.inv_temperature + gumbel(p.seed, gkey, len - sample_begin, i);
+      const float key = x * p.inv_temperature + gumbel(gseed, gkey, len - sample_begin, i);
       if (is_ts) {
         if (better(key, i, gs.v, gs.i)) { gs.v = key; gs.i = i; }
       } else {
@@ -585,6 +597,10 @@ void launch_logits_select(const SearchParams& p, int n_rows, hipStream_t st) {
   if ((p.hyp_begin != nullptr) != (p.hyp_maxlen != nullptr))
     throw std::runtime_error("logits_select: the per-hypothesis tables come as a pair");
   const bool rag = p.hyp_begin != nullptr;
+  if ((p.hyp_seed != nullptr) != (p.hyp_key != nullptr))
+    throw std::runtime_error("logits_select: the per-hypothesis seed tables come as a pair");
+  if (p.hyp_seed && p.mode != 2) throw std::runtime_error("logits_select: per-window seeds need sampling");
+  const bool seeded = p.hyp_seed != nullptr;
   const dim3 g(n_rows), b(SB);
 #define SEL_LAUNCH(MODE, REC, RULES)                                                                      \
   do {                                                                                                    \
@@ -597,18 +613,33 @@ void launch_logits_select(const SearchParams& p, int n_rows, hipStream_t st) {
       hipLaunchKernelGGL((logits_select_kernel<MODE, REC, RULES, false>), g, b, 0, st, p);                \
     }                                                                                                     \
   } while (0)
+  // sampling: the same choice, and with per-window seeds the SEED instantiations
+#define SEL_LAUNCH_S(REC, RULES)                                                                               \
+  do {                                                                                                         \
+    if (!seeded) {                                                                                             \
+      SEL_LAUNCH(2, REC, RULES);                                                                               \
+    } else if (RULES && bias) {                                                                                \
+      if (rag) hipLaunchKernelGGL((logits_select_kernel<2, REC, true, true, true, true>), g, b, 0, st, p);     \
+      else hipLaunchKernelGGL((logits_select_kernel<2, REC, true, false, true, true>), g, b, 0, st, p);        \
+    } else if (rag) {                                                                                          \
+      hipLaunchKernelGGL((logits_select_kernel<2, REC, RULES, true, false, true>), g, b, 0, st, p);            \
+    } else {                                                                                                   \
+      hipLaunchKernelGGL((logits_select_kernel<2, REC, RULES, false, false, true>), g, b, 0, st, p);           \
+    }                                                                                                          \
+  } while (0)
   switch ((rules ? 6 : 0) + p.mode * 2 + (rec ? 1 : 0)) {
     case 0: SEL_LAUNCH(0, false, false); break;
     case 1: SEL_LAUNCH(0, true, false); break;
     case 2: case 3: SEL_LAUNCH(1, false, false); break;
-    case 4: SEL_LAUNCH(2, false, false); break;
-    case 5: SEL_LAUNCH(2, true, false); break;
+    case 4: SEL_LAUNCH_S(false, false); break;
+    case 5: SEL_LAUNCH_S(true, false); break;
     case 6: SEL_LAUNCH(0, false, true); break;
     case 7: SEL_LAUNCH(0, true, true); break;
     case 8: case 9: SEL_LAUNCH(1, false, true); break;
-    case 10: SEL_LAUNCH(2, false, true); break;
-    default: SEL_LAUNCH(2, true, true); break;
+    case 10: SEL_LAUNCH_S(false, true); break;
+    default: SEL_LAUNCH_S(true, true); break;
   }
+#undef SEL_LAUNCH_S
 #undef SEL_LAUNCH
   WM_LAUNCH_CHECK("logits_select_kernel");
 }
@@ -620,7 +651,9 @@ __global__ __launch_bounds__(256) void hyp_start_kernel(const int* __restrict__ 
                                                         int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out,
                                                         const int* __restrict__ win_len,
                                                         const int* __restrict__ win_maxlen, int* hyp_begin,
-                                                        int* hyp_maxlen) {
+                                                        int* hyp_maxlen,
+                                                        const unsigned long long* __restrict__ win_seed,
+                                                        unsigned long long* hyp_seed, int* hyp_key) {
   const int h = hs[blockIdx.x], w = ws[blockIdx.x];
   // ragged prompts: P is the row stride of win_prompt, the window's own length comes from win_len (the padding
   // behind it is not read) and the slot's rows of the selection tables are filled here
@@ -630,6 +663,10 @@ __global__ __launch_bounds__(256) void hyp_start_kernel(const int* __restrict__ 
     if (win_len) {
       hyp_begin[h] = n;
       hyp_maxlen[h] = win_maxlen[w];
+    }
+    if (win_seed) {                            // per-window seeds: the slot draws as its window's hypothesis 0
+      hyp_seed[h] = win_seed[w];
+      hyp_key[h] = 0;
     }
     seq_len[h] = n;
     done[h] = 0;
@@ -641,11 +678,13 @@ __global__ __launch_bounds__(256) void hyp_start_kernel(const int* __restrict__ 
 
 void launch_hyp_start(int n, const int* hs, const int* ws, const int* win_prompt, int P, const int* win_slot, int n_ctx,
                       int* tokens, int* seq_len, int* done, float* cum, int* hyp_slot, int* hyp_out, hipStream_t st,
-                      const int* win_len, const int* win_maxlen, int* hyp_begin, int* hyp_maxlen) {
+                      const int* win_len, const int* win_maxlen, int* hyp_begin, int* hyp_maxlen,
+                      const unsigned long long* win_seed, unsigned long long* hyp_seed, int* hyp_key) {
   if (n <= 0) return;
   if (win_len && (!win_maxlen || !hyp_begin || !hyp_maxlen)) throw std::runtime_error("hyp_start: incomplete ragged tables");
+  if (win_seed && (!hyp_seed || !hyp_key)) throw std::runtime_error("hyp_start: incomplete seed tables");
   hipLaunchKernelGGL(hyp_start_kernel, dim3(n), dim3(64), 0, st, hs, ws, win_prompt, P, win_slot, n_ctx, tokens, seq_len,
-                     done, cum, hyp_slot, hyp_out, win_len, win_maxlen, hyp_begin, hyp_maxlen);
+                     done, cum, hyp_slot, hyp_out, win_len, win_maxlen, hyp_begin, hyp_maxlen, win_seed, hyp_seed, hyp_key);
   WM_LAUNCH_CHECK("hyp_start_kernel");
 }
 

@@ -362,8 +362,8 @@ class GpuEngine:
                  compact: bool = False, record_logprobs: bool = False, stats: Optional[dict] = None,
                  repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  prompt_lens: Optional[Sequence[int]] = None,
-                 sequence_bias: Optional[Sequence[Tuple[Sequence[int], float]]] = None
-                 ) -> Tuple[List[GenResult], int]:
+                 sequence_bias: Optional[Sequence[Tuple[Sequence[int], float]]] = None,
+                 seeds: Optional[Sequence[int]] = None) -> Tuple[List[GenResult], int]:
         """ctranslate2 Whisper.generate over windows in slots (wm_generate).  max_rows / compact: the row-set decode
         (greedy / one sampled hypothesis; windows refill finished rows in the given order, include/whisper_mi355.h);
         beam search with compact drops finished windows' hypotheses from the passes.
@@ -380,8 +380,16 @@ class GpuEngine:
         (prompt included).  prompt_lens: the prompts are rows of one length already and window w's prompt is the first
         prompt_lens[w] tokens of its row (the padding is passed as it is: the engine neither reads nor validates it).
         A call whose prompts share one length, with an int max_length and sot_index and no prompt_lens, builds the
-        one-length arguments (NULL for the three per-window pointers)."""
+        one-length arguments (NULL for the three per-window pointers).
+        seeds: one sampling seed per window (wm_generate_seeded; each taken mod 2^64 like `seed`, which is then not
+        read): window w's hypothesis j draws its noise from (seeds[w], j), so the window's result is that of a call
+        with it alone and seed=seeds[w], wherever it stands in the call.  None calls wm_generate."""
         W = len(slots)
+        h_seeds = None
+        if seeds is not None:
+            if len(seeds) != W:
+                raise ValueError("seeds needs one seed per window")
+            h_seeds = np.ascontiguousarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
         st = self.dims.specials
         if prompt_lens is not None:
             lens_in = [int(n) for n in prompt_lens]
@@ -445,7 +453,11 @@ class GpuEngine:
             if sequence_bias:
                 self.set_sequence_bias(sequence_bias)
             try:
-                _capi.check(self.lib.wm_generate(self.h, C.byref(a), self.stream_ptr()), "wm_generate")
+                if h_seeds is None:
+                    _capi.check(self.lib.wm_generate(self.h, C.byref(a), self.stream_ptr()), "wm_generate")
+                else:
+                    _capi.check(self.lib.wm_generate_seeded(self.h, C.byref(a), h_seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                            self.stream_ptr()), "wm_generate_seeded")
             finally:
                 if sequence_bias:
                     self.set_sequence_bias(())

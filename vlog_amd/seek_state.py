@@ -47,33 +47,80 @@ def window_max_length(prompt: Sequence[int], max_new_tokens: Optional[int], mode
     return max_length
 
 
+ACCEPTED, NEXT, EXHAUSTED = "accepted", "next", "exhausted"
+
+
+class FallbackLadder:
+    """faster-whisper generate_with_fallback as a resumable object, so a driver can hold one per window and decode
+    the windows that fail a temperature together (decode_round_levels) instead of looping over one window.
+
+      request()      -> (temperature, seed) of the decode whose result the ladder waits for: temperature `level` of
+                        options.temperatures with seed + level
+      judge(result)  -> ACCEPTED (the result stands), NEXT (it needs a fallback: request() names the next decode) or
+                        EXHAUSTED (every temperature failed: the best of those below the compression-ratio
+                        threshold, or of all, stands, reported at the last temperature)
+      result()       -> (result, avg_logprob, temperature, compression_ratio), once `done`
+
+    `done` is set from the start when the temperature list is empty; result() then fails as the loop form did."""
+
+    def __init__(self, decode_text: Callable[[Sequence[int]], str], options, seed: int = 0):
+        self.decode_text = decode_text
+        self.options = options
+        self.seed = seed
+        self.level = 0
+        self.done = not options.temperatures
+        self._all: List[tuple] = []
+        self._below_cr: List[tuple] = []
+        self._decode: Optional[tuple] = None
+
+    def request(self) -> Tuple[float, int]:
+        if self.done:
+            raise RuntimeError("FallbackLadder.request after the ladder ended")
+        return self.options.temperatures[self.level], self.seed + self.level
+
+    def judge(self, result) -> str:
+        if self.done:
+            raise RuntimeError("FallbackLadder.judge after the ladder ended")
+        o = self.options
+        temperature = o.temperatures[self.level]
+        n = len(result.tokens)
+        avg_lp = segs.avg_logprob(result.score, n, o.length_penalty)
+        text = self.decode_text(result.tokens).strip()
+        cr = segs.compression_ratio(text)
+        decode_result = (result, avg_lp, temperature, cr)
+        self._all.append(decode_result)
+        fb, below = segs.needs_fallback(cr, avg_lp, result.no_speech_prob, o.compression_ratio_threshold,
+                                        o.log_prob_threshold, o.no_speech_threshold)
+        if below:
+            self._below_cr.append(decode_result)
+        if not fb:
+            self._decode, self.done = decode_result, True
+            return ACCEPTED
+        if self.level + 1 < len(o.temperatures):
+            self.level += 1
+            return NEXT
+        best = max(self._below_cr or self._all, key=lambda x: x[1])
+        self._decode, self.done = (best[0], best[1], temperature, best[3]), True
+        return EXHAUSTED
+
+    def result(self) -> tuple:
+        if not self.done:
+            raise RuntimeError("FallbackLadder.result before the ladder ended")
+        if self._decode is None:                # no temperature at all: nothing to choose from
+            raise ValueError("fallback ladder without temperatures")
+        return self._decode
+
+
 def fallback_ladder(generate: Callable[[float, int], object], decode_text: Callable[[Sequence[int]], str], options,
                     seed: int = 0, first=None):
     """faster-whisper generate_with_fallback -> (result, avg_logprob, temperature, compression_ratio).
     generate(temperature, seed) -> an object with tokens / score / no_speech_prob; temperature i runs with seed + i.
     `first`: the result at temperatures[0] when a shared pass already computed it (the ladder then starts by judging
-    it, and calls generate only for the temperatures after it)."""
-    all_results, below_cr = [], []
-    decode_result = None
-    temperature = options.temperatures[0] if options.temperatures else 0.0
-    for i, temperature in enumerate(options.temperatures):
-        result = first if (i == 0 and first is not None) else generate(temperature, seed + i)
-        n = len(result.tokens)
-        avg_lp = segs.avg_logprob(result.score, n, options.length_penalty)
-        text = decode_text(result.tokens).strip()
-        cr = segs.compression_ratio(text)
-        decode_result = (result, avg_lp, temperature, cr)
-        all_results.append(decode_result)
-        fb, below = segs.needs_fallback(cr, avg_lp, result.no_speech_prob, options.compression_ratio_threshold,
-                                        options.log_prob_threshold, options.no_speech_threshold)
-        if below:
-            below_cr.append(decode_result)
-        if not fb:
-            break
-    else:
-        best = max(below_cr or all_results, key=lambda x: x[1])
-        decode_result = (best[0], best[1], temperature, best[3])
-    return decode_result
+    it, and calls generate only for the temperatures after it).  The loop over one FallbackLadder."""
+    ladder = FallbackLadder(decode_text, options, seed)
+    while not ladder.done:
+        ladder.judge(first if (ladder.level == 0 and first is not None) else generate(*ladder.request()))
+    return ladder.result()
 
 
 def _get_end(segments: List[dict]) -> Optional[float]:
@@ -254,6 +301,36 @@ def decode_round_with(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
         decode = fallback_ladder(lambda t, seed, i=i: fallback_generate(i, t, seed), state.tokenizer.decode, state.options,
                                  seed=req.window, first=firsts[i])
         emit(f, state.consume(decode, (lambda cur, size, last, i=i: align(i, cur, size, last)) if align else None))
+
+
+def decode_round_levels(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
+                        first_pass: Callable[[List[int]], List[object]],
+                        level_pass: Callable[[List[int], float, List[int]], List[object]],
+                        align: Optional[Callable[[int, List[dict], int, float], float]],
+                        emit: Callable[[int, List[dict]], None]) -> None:
+    """decode_round_with with the fallback ladder walked by LEVELS: the entries whose result at temperature i - 1
+    needs a fallback are re-decoded together.
+    first_pass(indices): as decode_round_with.  level_pass(indices, temperature, seeds) -> the results of those
+    entries at `temperature`, entry k with seeds[k]; level i is called once, with the entries still failing in batch
+    order, temperatures[i] (the list is common to the round's entries) and seeds [req.window + i]; an accepted entry
+    never appears again, and a level nobody needs is not called.  Once no entry is left, every entry is consumed and
+    emitted in batch order, word-aligned (align, at consume time) against its own slot.  Per entry the decode tuple
+    is what fallback_ladder returns for the same results."""
+    firsts = first_pass(list(range(len(batch))))
+    ladders = [FallbackLadder(state.tokenizer.decode, state.options, seed=req.window) for _, state, req in batch]
+    failing = [i for i, ladder in enumerate(ladders) if not ladder.done and ladder.judge(firsts[i]) == NEXT]
+    while failing:
+        requests = [ladders[i].request() for i in failing]
+        temperature = requests[0][0]
+        if any(t != temperature for t, _ in requests):
+            raise ValueError("decode_round_levels: the entries of a round must share one temperature list")
+        results = level_pass(list(failing), temperature, [s for _, s in requests])
+        if len(results) != len(failing):
+            raise RuntimeError("decode_round_levels: level_pass must return one result per entry")
+        failing = [i for i, r in zip(failing, results) if ladders[i].judge(r) == NEXT]
+    for i, (f, state, req) in enumerate(batch):
+        emit(f, state.consume(ladders[i].result(),
+                              (lambda cur, size, last, i=i: align(i, cur, size, last)) if align else None))
 
 
 # ---------------------------------------------------------------------------------------------------- sections

@@ -36,8 +36,8 @@ import torch
 from . import segments as segs
 from .segments import _word_means, merge_punctuations
 from .audio import mono_f32, read_wav
-from .seek_state import (ENERGY_FRAME_MEL, MAX_SECTIONS, SeekState, chunk_joins, decode_round_with, fallback_ladder,
-                         iter_lockstep, plan_sections, run_lockstep, window_max_length)
+from .seek_state import (ENERGY_FRAME_MEL, MAX_SECTIONS, SeekState, chunk_joins, decode_round_levels, decode_round_with,
+                         fallback_ladder, iter_lockstep, plan_sections, run_lockstep, window_max_length)
 from .dims import CHUNK_LENGTH, HOP_LENGTH, N_FRAMES, SAMPLE_RATE, TIME_PRECISION
 from .tokenizer import Tokenizer
 from .weights import resolve_model
@@ -110,6 +110,7 @@ class TranscriptionOptions:
     section_frames: Optional[List[Tuple[int, int]]] = None     # transcribe(sections=N): the (start, end) chosen
     sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None   # as passed (or the environment file's)
     sequence_bias_table: Optional[List[Tuple[Tuple[int, ...], float]]] = None     # ... as the engine takes it
+    lockstep_fallback: bool = False     # the fallback temperatures of a lockstep round decode by levels (as resolved)
 
 
 @dataclass
@@ -151,6 +152,17 @@ class _GenOut:
     tokens: List[int]
     score: float
     no_speech_prob: float
+
+
+def _resolve_lockstep_fallback(value: Optional[bool]) -> bool:
+    """The lockstep_fallback argument of transcribe / transcribe_many: None reads VLOG_AMD_LOCKSTEP_FALLBACK (0 / 1;
+    unset or empty: off)."""
+    if value is not None:
+        return bool(value)
+    env = os.environ.get("VLOG_AMD_LOCKSTEP_FALLBACK", "")
+    if env not in ("", "0", "1"):
+        raise ValueError(f"VLOG_AMD_LOCKSTEP_FALLBACK must be 0 or 1, got {env!r}")
+    return env == "1"
 
 
 def _resolve_device_index(device: str, device_index) -> int:
@@ -342,8 +354,9 @@ class WhisperModel:
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
                    language_detection_segments: int = 1, sections: Optional[int] = None,
                    sections_in_flight: Optional[int] = None,
-                   sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None):
-        """faster-whisper's `WhisperModel.transcribe`, plus three arguments of this engine:
+                   sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None,
+                   lockstep_fallback: Optional[bool] = None):
+        """faster-whisper's `WhisperModel.transcribe`, plus four arguments of this engine:
 
         sequence_bias: {phrase or token tuple: bias}, deterministic custom-vocabulary boosts (bias > 0) and soft or
         hard bans (bias < 0; -100 is a ban) applied on the device at every decode step of every decode form (beam
@@ -373,7 +386,17 @@ class WhisperModel:
         8 -> 476 / 30.0 / 3.11, 16 (13 after the 30 s rule) -> 551 / 48.3 / 3.50; the same 13 sections one after
         another (sections_in_flight=1): 103.  The doublings gain x1.65, 1.46, 1.38, 1.16 (every cut adds a short
         window, and load, VAD and log-mel are not shared), so by the rule of transcribe_many's max_files (the last
-        doubling that gains at least x1.5) the recommended value is 2; the default stays 1."""
+        doubling that gains at least x1.5) the recommended value is 2; the default stays 1.
+
+        lockstep_fallback: how a lockstep round (sections > 1; one window per round has nothing to share) decodes the
+        windows that need a fallback temperature.  False: each alone, with generate_with_fallback's calls, bit-identical
+        to the one-file loop.  True: by levels, the windows that fail temperature i together in ONE seeded
+        engine.generate at temperature i + 1 (rows = failing windows x best_of, every window with its own seed
+        window + i + 1; a sampled first pass is one such call too).  A window's rows then share decoder passes with
+        other windows' rows, so its result agrees with the solo decode to f32 rounding, not bit for bit.  Default: the
+        VLOG_AMD_LOCKSTEP_FALLBACK environment variable (0 / 1), else False.  Echoed in
+        info.transcription_options.lockstep_fallback.  Throughput mode has its own batched re-decode and ignores it.
+        Measurement: DESIGN.md §8 (tools/bench_worker_call.py --lockstep-fallback)."""
         for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
             if val != default:
@@ -392,6 +415,7 @@ class WhisperModel:
             raise ValueError("sections > 1 is the sequential mode's; throughput mode cuts the file its own way")
         if sections > 1 and clip_timestamps not in ("0", [0], [0.0]):
             raise ValueError("sections > 1 cannot be combined with clip_timestamps")
+        lockstep_fallback = _resolve_lockstep_fallback(lockstep_fallback)
         if self.throughput:
             # opt-in throughput mode for the UNCHANGED worker (VLOG_AMD_THROUGHPUT=1): its call
             # transcribe(wav, language, task, beam_size=5, vad_filter=True) runs as BatchedInferencePipeline:
@@ -427,6 +451,7 @@ class WhisperModel:
             hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hotwords,
             language_detection_threshold=language_detection_threshold,
             language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
+        options.lockstep_fallback = lockstep_fallback
         bounds = self._plan_sections(audio, features, speech_chunks, sections) if sections > 1 else None
         if bounds is not None:
             options.section_frames = bounds
@@ -572,14 +597,19 @@ class WhisperModel:
         """One round of run_lockstep on the GPU, for transcribe_many (items = files, each with its own log-mel,
         features_of(item)) and for the sections of one file (`shared`: the one log-mel every item reads).
         batch: [(item, state, request)], entry i = cross slot i.  Reserve, ONE encoder call, cross_kv into slots
-        0..nb-1, the ragged first pass at temperatures[0] grouped by suppress list, the solo fallback passes, per-item
-        word alignment; emit(item, segment dicts).  reserved: [slots reserved by the caller's earlier rounds]."""
+        0..nb-1, the ragged first pass at temperatures[0] grouped by suppress list, the fallback passes (solo, or with
+        options.lockstep_fallback by levels: the windows that fail a temperature re-decode in one seeded generate per
+        suppress list against the slots the round filled), per-item word alignment; emit(item, segment dicts).
+        reserved: [slots reserved by the caller's earlier rounds]."""
         nb = len(batch)
         opt0 = batch[0][1].options              # everything but the per-file prompt parts is common to the items
         temps = opt0.temperatures
         t0 = temps[0] if temps else 0.0
         sampling = t0 > 0
-        per = (opt0.best_of if sampling else opt0.beam_size)
+        levels = bool(opt0.lockstep_fallback)
+        # by levels a round may decode nb windows x best_of rows: reserved once, so no level re-allocates the
+        # hypothesis state while the slots are in use
+        per = max(opt0.beam_size, opt0.best_of) if levels else (opt0.best_of if sampling else opt0.beam_size)
         mit = int(round(opt0.max_initial_timestamp / self.time_precision))
         sot = self.dims.specials.sot
         with self._lock:                        # one lock scope per round: the slots hold this round's windows
@@ -600,30 +630,41 @@ class WhisperModel:
                 enc = self.engine.encode(mel, [i * N_FRAMES for i in range(nb)], [req.size for _, _, req in batch])
             self.engine.cross_kv(enc, 0)
 
+            def shared_pass(idx, t, seeds=None):
+                """entries idx decoded together at temperature t, one generate per suppress list; seeds (sampling):
+                one per entry, so every window draws as in a call of its own (engine.generate seeds)"""
+                out: List[Optional[_GenOut]] = [None] * len(idx)
+                groups: dict = {}
+                for k, i in enumerate(idx):     # the suppress list is one per generate call
+                    groups.setdefault(tuple(batch[i][1].options.suppress_tokens), []).append(k)
+                for sup, ks in groups.items():
+                    members = [idx[k] for k in ks]
+                    prompts = [batch[i][2].prompt for i in members]
+                    kw = {}
+                    if t > 0:                   # the arguments _generate passes for a sampled decode
+                        kw = dict(num_hypotheses=opt0.best_of, seeds=[seeds[k] for k in ks])
+                    res, _ = self.engine.generate(
+                        members, prompts, beam_size=1 if t > 0 else opt0.beam_size, patience=opt0.patience,
+                        length_penalty=opt0.length_penalty, max_length=[batch[i][2].max_length for i in members],
+                        temperature=t, suppress_tokens=list(sup),
+                        suppress_blank=opt0.suppress_blank, max_initial_timestamp_index=mit,
+                        with_timestamps=not opt0.without_timestamps,
+                        sot_index=[p.index(sot) if sot in p else -1 for p in prompts], check_every=4,
+                        repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size,
+                        sequence_bias=opt0.sequence_bias_table, **kw)
+                    for k, r in zip(ks, res):
+                        out[k] = _GenOut(r.tokens, r.score, r.no_speech_prob)
+                return out
+
             def first_pass(idx):
+                if sampling and levels:
+                    return shared_pass(idx, t0, [batch[i][2].window for i in idx])
                 if sampling:
                     # a sampled pass draws noise keyed on (seed, hypothesis index): a file's draws would depend on
                     # its place in the round, so each window decodes alone, with generate_with_fallback's call
                     return [self._generate(batch[i][2].prompt, batch[i][1].options, t0, batch[i][2].max_length,
                                            batch[i][2].window, slot=i) for i in idx]
-                out: List[Optional[_GenOut]] = [None] * len(idx)
-                groups: dict = {}
-                for i in idx:                   # the suppress list is one per generate call
-                    groups.setdefault(tuple(batch[i][1].options.suppress_tokens), []).append(i)
-                for sup, members in groups.items():
-                    prompts = [batch[i][2].prompt for i in members]
-                    res, _ = self.engine.generate(
-                        members, prompts, beam_size=opt0.beam_size, patience=opt0.patience,
-                        length_penalty=opt0.length_penalty, max_length=[batch[i][2].max_length for i in members],
-                        temperature=t0, suppress_tokens=list(sup),
-                        suppress_blank=opt0.suppress_blank, max_initial_timestamp_index=mit,
-                        with_timestamps=not opt0.without_timestamps,
-                        sot_index=[p.index(sot) if sot in p else -1 for p in prompts], check_every=4,
-                        repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size,
-                        sequence_bias=opt0.sequence_bias_table)
-                    for i, r in zip(members, res):
-                        out[i] = _GenOut(r.tokens, r.score, r.no_speech_prob)
-                return out
+                return shared_pass(idx, t0)
 
             def fallback_generate(i, t, seed):
                 _, state, req = batch[i]
@@ -635,7 +676,10 @@ class WhisperModel:
                 return self.add_word_timestamps([current], state.tokenizer, size, o.prepend_punctuations,
                                                 o.append_punctuations, last, slots=[i])
 
-            decode_round_with(batch, first_pass, fallback_generate, align if opt0.word_timestamps else None, emit)
+            if levels:
+                decode_round_levels(batch, first_pass, shared_pass, align if opt0.word_timestamps else None, emit)
+            else:
+                decode_round_with(batch, first_pass, fallback_generate, align if opt0.word_timestamps else None, emit)
 
     def _generate_sections(self, features: torch.Tensor, tokenizer: Tokenizer, options: TranscriptionOptions,
                            bounds: Sequence[Tuple[int, int]], in_flight: int):
@@ -687,7 +731,8 @@ class WhisperModel:
                         hallucination_silence_threshold: Optional[float] = None, hotwords=None,
                         language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                         max_files: int = 16,
-                        sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None):
+                        sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None,
+                        lockstep_fallback: Optional[bool] = None):
         """`transcribe` for several files at once in the sequential (parity) mode -> [(list_of_segments, info)] in
         input order; each file gets what `transcribe(file, same arguments)` gives for it alone.
 
@@ -709,6 +754,9 @@ class WhisperModel:
         cost, so every doubling still pays (x1.80, 1.52, 1.62, 1.56, 1.49), while each file's own latency grows (2.3 s
         alone, 5.2 s at 16, 7.0 s at 32 for a 5-minute clip).  The default is the last doubling that gains at least
         x1.5 (the 16-files line); a worker that only wants throughput can pass 32.
+        lockstep_fallback (see `transcribe`; default VLOG_AMD_LOCKSTEP_FALLBACK, else False): True decodes the
+        fallback temperatures by levels, the round's failing windows together in one seeded generate per temperature;
+        each file then gets what `transcribe` gives for it alone to f32 rounding, not bit for bit.
         With throughput mode on, this is BatchedInferencePipeline.transcribe_many."""
         for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
@@ -723,6 +771,7 @@ class WhisperModel:
             raise ValueError("max_files must be >= 1")
         if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
             raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
+        lockstep_fallback = _resolve_lockstep_fallback(lockstep_fallback)
 
         def per_file(v, name):
             if isinstance(v, (list, tuple)):
@@ -771,6 +820,7 @@ class WhisperModel:
                 hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hot[f],
                 language_detection_threshold=language_detection_threshold,
                 language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
+            options.lockstep_fallback = lockstep_fallback
             files[f] = [features, info, chunks]
             return SeekState(features.shape[1] - 1, tokenizer, options, self.max_length, self.frames_per_second)
 
