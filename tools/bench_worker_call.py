@@ -30,6 +30,12 @@ at every point, alternated call by call inside the same process (--sections: --r
 flag.  Every line then also splits engine.generate's counters (wm_generate h_stats, per call) into the first passes
 (temperature 0) and the fallback passes (temperature > 0): calls, decoder passes, rows per pass, ms per pass.  Without
 the option the argument is not passed at all, so the same file measures a tree from before it.
+
+--max-line-width W (with --sections): caption shaping (transcribe's max_line_width) off and on at every point,
+alternated call by call inside the same process as the two --lockstep-fallback flags are: max_line_width=0, then
+max_line_width=W with transcribe's defaults for the line count and the cue length; one JSON line per arm with
+"max_line_width" 0 or W (the lines of profiles/worker_call_captions.jsonl).  Without the option the argument is not
+passed at all.
 """
 import argparse
 import json
@@ -121,15 +127,32 @@ def sectioned(model, args, spec, tmp):
     write_wav(path, np.concatenate([speech_like(30.0, i) for i in range(n_win)]))
     audio_s = n_win * 30.0
     acc = time_generate(model.engine)
+    aligned = {"s": 0.0, "calls": 0, "groups": 0}       # engine.align_batch: the word alignment shaping turns on
+    inner_align = model.engine.align_batch
 
-    flags = fallback_flags(args)
+    def timed_align(slots, *a, **kw):
+        t = time.perf_counter()
+        r = inner_align(slots, *a, **kw)
+        aligned["s"] += time.perf_counter() - t
+        aligned["calls"] += 1
+        aligned["groups"] += len(slots)
+        return r
 
-    def call(n, flag=None):
+    model.engine.align_batch = timed_align
+
+    # the arms timed at every point: (lockstep_fallback, max_line_width), None = the argument is not passed
+    widths = [None] if args.max_line_width is None else [0, args.max_line_width]
+    flags = [(f, w) for f in fallback_flags(args) for w in widths]
+
+    def call(n, arm=(None, None)):
+        flag, width = arm
         kw = dict(language=None, task="transcribe", beam_size=5, vad_filter=True)
         if args.temperature is not None:
             kw["temperature"] = args.temperature
         if flag is not None:
             kw["lockstep_fallback"] = bool(flag)
+        if width is not None:
+            kw["max_line_width"] = width
         if n > 0:
             kw["sections"] = n
             if args.sections_in_flight is not None:
@@ -139,21 +162,26 @@ def sectioned(model, args, spec, tmp):
         segs = [{"start": s.start, "end": s.end, "text": s.text} for s in segments]
         generate_webvtt(segs)
         dt = time.perf_counter() - t
-        print(f"sections={n} lockstep_fallback={flag}: {dt:.3f} s", file=sys.stderr, flush=True)    # progress
+        print(f"sections={n} lockstep_fallback={flag} max_line_width={width}: {dt:.3f} s", file=sys.stderr,
+              flush=True)                                                  # progress
         return dt, info, len(segs)
 
     call(0)                                                        # warm-up (allocations, kernels)
     for n in counts:
         for flag in flags:
             call(n, flag)                                          # (the slots and rows of this point)
-        # the flags alternate call by call, so drift of the box lands on both; counters are kept per flag
+        # the arms alternate call by call, so drift of the box lands on both; counters are kept per flag
         accs = {flag: dict(ACC_ZERO) for flag in flags}
         walls = {flag: [] for flag in flags}
+        aligns = {flag: {"s": 0.0, "calls": 0, "groups": 0} for flag in flags}
         last = {}
         for _ in range(args.repeats):
             for flag in flags:
                 acc.update(ACC_ZERO)
+                aligned.update(s=0.0, calls=0, groups=0)
                 dt, info, nseg = call(n, flag)
+                for k in aligned:
+                    aligns[flag][k] += aligned[k]
                 walls[flag].append(dt)
                 last[flag] = (info, nseg)
                 for k in ACC_ZERO:
@@ -172,9 +200,16 @@ def sectioned(model, args, spec, tmp):
                     "generate_calls": a["calls"] // args.repeats, "decoder_passes": a["passes"] // args.repeats,
                     "ms_per_decoder_pass": round(1e3 * a["s"] / max(a["passes"], 1), 4),
                     "rows_per_pass": round(a["rows"] / max(a["passes"], 1), 2)}
-            if flag is not None:
-                line["lockstep_fallback"] = flag
+            if flag[0] is not None:
+                line["lockstep_fallback"] = flag[0]
                 line.update(split_stats(a, args.repeats))
+            if flag[1] is not None:
+                line["max_line_width"] = flag[1]
+                line["word_timestamps"] = bool(info.transcription_options.word_timestamps)
+                al = aligns[flag]
+                line["align"] = {"calls": al["calls"] // args.repeats, "windows": al["groups"] // args.repeats,
+                                 "s": round(al["s"] / args.repeats, 3),
+                                 "ms_per_window": round(1e3 * al["s"] / max(al["groups"], 1), 3)}
             print(json.dumps(line), flush=True)
 
 
@@ -236,7 +271,12 @@ def main():
     ap.add_argument("--lockstep-fallback", default=None,
                     help="0, 1 or 0,1: the lockstep_fallback argument at every --sections / --files point (module "
                          "docstring); default: the argument is not passed")
+    ap.add_argument("--max-line-width", type=int, default=None,
+                    help="with --sections: time caption shaping off (max_line_width=0) and on (this width) at every "
+                         "point, alternated call by call (module docstring); default: the argument is not passed")
     args = ap.parse_args()
+    if args.max_line_width is not None and (not args.sections or args.max_line_width < 1):
+        raise SystemExit("--max-line-width takes a width >= 1 and goes with --sections")
     spec = f"synthetic:{args.model}:0" + ("" if args.random_weights else ":margin")
     model = WhisperModel(spec, device="cpu", compute_type="int8", eot_after=110)
     if args.no_graph:

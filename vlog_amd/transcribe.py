@@ -36,6 +36,7 @@ import torch
 from . import segments as segs
 from .segments import _word_means, merge_punctuations
 from .audio import mono_f32, read_wav
+from .captions import resolve_caption_options, set_word_tokens, shape_captions
 from .seek_state import (ENERGY_FRAME_MEL, MAX_SECTIONS, SeekState, chunk_joins, decode_round_levels, decode_round_with,
                          fallback_ladder, iter_lockstep, plan_sections, run_lockstep, window_max_length)
 from .dims import CHUNK_LENGTH, HOP_LENGTH, N_FRAMES, SAMPLE_RATE, TIME_PRECISION
@@ -111,6 +112,9 @@ class TranscriptionOptions:
     sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None   # as passed (or the environment file's)
     sequence_bias_table: Optional[List[Tuple[Tuple[int, ...], float]]] = None     # ... as the engine takes it
     lockstep_fallback: bool = False     # the fallback temperatures of a lockstep round decode by levels (as resolved)
+    max_line_width: Optional[int] = None        # caption shaping (captions.shape_captions) as in force; None: off.
+    max_line_count: Optional[int] = None        # ... while it is on, word_timestamps reads True
+    max_cue_seconds: Optional[float] = None
 
 
 @dataclass
@@ -163,6 +167,31 @@ def _resolve_lockstep_fallback(value: Optional[bool]) -> bool:
     if env not in ("", "0", "1"):
         raise ValueError(f"VLOG_AMD_LOCKSTEP_FALLBACK must be 0 or 1, got {env!r}")
     return env == "1"
+
+
+def _word(w: dict) -> Word:
+    """An aligned word dict of add_word_timestamps -> Word.  The word's text tokens ride along outside the dataclass
+    fields (captions.word_tokens), so caption shaping can give every cue its own tokens."""
+    word = Word(start=w["start"], end=w["end"], word=w["word"], probability=w["probability"])
+    if "tokens" in w:
+        set_word_tokens(word, w["tokens"])
+    return word
+
+
+def _caption_options(max_line_width, max_line_count, max_cue_seconds) -> dict:
+    """The caption arguments of a transcribe call -> the keyword arguments that carry them on, resolved against the
+    environment once: the three TranscriptionOptions fields, and word_timestamps=True when shaping is on."""
+    caps = resolve_caption_options(max_line_width, max_line_count, max_cue_seconds, os.environ)
+    if caps is None:
+        return dict(max_line_width=0)
+    return dict(max_line_width=caps[0], max_line_count=caps[1], max_cue_seconds=caps[2], word_timestamps=True)
+
+
+def _shaped(segments, options: TranscriptionOptions):
+    """The last stage of every segment stream: shape_captions when the options have it on."""
+    if not options.max_line_width:
+        return segments
+    return shape_captions(segments, options.max_line_width, options.max_line_count, options.max_cue_seconds)
 
 
 def _resolve_device_index(device: str, device_index) -> int:
@@ -355,8 +384,22 @@ class WhisperModel:
                    language_detection_segments: int = 1, sections: Optional[int] = None,
                    sections_in_flight: Optional[int] = None,
                    sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None,
-                   lockstep_fallback: Optional[bool] = None):
-        """faster-whisper's `WhisperModel.transcribe`, plus four arguments of this engine:
+                   lockstep_fallback: Optional[bool] = None, max_line_width: Optional[int] = None,
+                   max_line_count: Optional[int] = None, max_cue_seconds: Optional[float] = None):
+        """faster-whisper's `WhisperModel.transcribe`, plus these arguments of this engine:
+
+        max_line_width, max_line_count, max_cue_seconds: caption shaping (vlog_amd/captions.py).  With a width > 0 the
+        call decodes exactly as the same call with word_timestamps=True (the shaper needs word times; they move the
+        seek to the last word's end, as they do today), and the final stream, after the VAD's times are restored, is
+        cut into cues of at most max_line_count (default 2, 1..4) lines of at most max_line_width characters, the
+        lines of a cue joined by "\n" in `text`; a cue also ends at a pause above 3 s, when it would last longer than
+        max_cue_seconds (default: no limit), and after a sentence end once it is half full (captions.shape_captions
+        states the rule).  Every cue is a Segment with its own words and tokens and its source segment's statistics;
+        ids run 1, 2, ... over the cues.  max_line_width=None reads VLOG_AMD_MAX_LINE_WIDTH (unset: off), 0 turns
+        shaping off whatever the environment says; the other two read VLOG_AMD_MAX_LINE_COUNT and
+        VLOG_AMD_MAX_CUE_SECONDS while shaping is on, and raise ValueError when passed while it is off.  What is in
+        force is echoed in info.transcription_options (word_timestamps then reads True).  Every decode form takes
+        them: sections=N, transcribe_many (per file) and throughput mode.
 
         sequence_bias: {phrase or token tuple: bias}, deterministic custom-vocabulary boosts (bias > 0) and soft or
         hard bans (bias < 0; -100 is a ban) applied on the device at every decode step of every decode form (beam
@@ -416,6 +459,8 @@ class WhisperModel:
         if sections > 1 and clip_timestamps not in ("0", [0], [0.0]):
             raise ValueError("sections > 1 cannot be combined with clip_timestamps")
         lockstep_fallback = _resolve_lockstep_fallback(lockstep_fallback)
+        captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
+        word_timestamps = captions.pop("word_timestamps", word_timestamps)
         if self.throughput:
             # opt-in throughput mode for the UNCHANGED worker (VLOG_AMD_THROUGHPUT=1): its call
             # transcribe(wav, language, task, beam_size=5, vad_filter=True) runs as BatchedInferencePipeline:
@@ -433,7 +478,7 @@ class WhisperModel:
                 word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, **captions)
         if sections > 1 and not isinstance(audio, np.ndarray):
             audio = self._load_audio(audio)     # (the cuts without VAD are chosen on the samples)
         features, tokenizer, options, info, speech_chunks = self._prepare_file(
@@ -450,7 +495,7 @@ class WhisperModel:
             max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
             hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hotwords,
             language_detection_threshold=language_detection_threshold,
-            language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
+            language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, captions=captions)
         options.lockstep_fallback = lockstep_fallback
         bounds = self._plan_sections(audio, features, speech_chunks, sections) if sections > 1 else None
         if bounds is not None:
@@ -462,7 +507,7 @@ class WhisperModel:
         if speech_chunks:
             from .vad import restore_speech_timestamps
             gen = restore_speech_timestamps(gen, speech_chunks, SAMPLE_RATE)
-        return gen, info
+        return _shaped(gen, options), info
 
     def _plan_sections(self, audio: np.ndarray, features: torch.Tensor, speech_chunks, n: int) -> List[Tuple[int, int]]:
         """plan_sections for one prepared file: at the VAD chunk joins when VAD ran, else at the quietest 20 ms frames
@@ -483,8 +528,9 @@ class WhisperModel:
                       prefix, suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp,
                       word_timestamps, prepend_punctuations, append_punctuations, multilingual, vad_filter,
                       vad_parameters, max_new_tokens, clip_timestamps, hallucination_silence_threshold, hotwords,
-                      language_detection_threshold, language_detection_segments, sequence_bias=None):
+                      language_detection_threshold, language_detection_segments, sequence_bias=None, captions=None):
         """What `transcribe` does for one file before its seek loop: load, VAD, log-mel, language, tokenizer, options.
+        captions: _caption_options' dict (the caller has word_timestamps from it already).
         -> (features, tokenizer, options, info, speech_chunks)"""
         if not isinstance(audio, np.ndarray):
             audio = self._load_audio(audio)
@@ -531,6 +577,9 @@ class WhisperModel:
             append_punctuations=append_punctuations, multilingual=multilingual, max_new_tokens=max_new_tokens,
             clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
             hotwords=hotwords, sequence_bias=bias_map, sequence_bias_table=bias_table)
+        if captions and captions["max_line_width"]:
+            options.max_line_width, options.max_line_count = captions["max_line_width"], captions["max_line_count"]
+            options.max_cue_seconds = captions["max_cue_seconds"]
         info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
                                  duration_after_vad=duration_after_vad, all_language_probs=all_language_probs,
                                  transcription_options=options, vad_options=vad_opts)
@@ -572,7 +621,7 @@ class WhisperModel:
     # ------------------------------------------------------------------ seek loop
     def _segment(self, d: dict) -> Segment:
         words = d.pop("words")
-        return Segment(words=[Word(**w) for w in words] if words is not None else None, **d)
+        return Segment(words=[_word(w) for w in words] if words is not None else None, **d)
 
     def generate_segments(self, features: torch.Tensor, tokenizer: Tokenizer, options: TranscriptionOptions):
         """The one-file driver of vlog_amd/seek_state.py SeekState (faster-whisper generate_segments)."""
@@ -732,7 +781,8 @@ class WhisperModel:
                         language_detection_threshold: Optional[float] = 0.5, language_detection_segments: int = 1,
                         max_files: int = 16,
                         sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None,
-                        lockstep_fallback: Optional[bool] = None):
+                        lockstep_fallback: Optional[bool] = None, max_line_width: Optional[int] = None,
+                        max_line_count: Optional[int] = None, max_cue_seconds: Optional[float] = None):
         """`transcribe` for several files at once in the sequential (parity) mode -> [(list_of_segments, info)] in
         input order; each file gets what `transcribe(file, same arguments)` gives for it alone.
 
@@ -757,6 +807,8 @@ class WhisperModel:
         lockstep_fallback (see `transcribe`; default VLOG_AMD_LOCKSTEP_FALLBACK, else False): True decodes the
         fallback temperatures by levels, the round's failing windows together in one seeded generate per temperature;
         each file then gets what `transcribe` gives for it alone to f32 rounding, not bit for bit.
+        max_line_width, max_line_count, max_cue_seconds (see `transcribe`): caption shaping, applied to every file's
+        segments on their own (ids 1, 2, ... per file).
         With throughput mode on, this is BatchedInferencePipeline.transcribe_many."""
         for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
@@ -772,6 +824,8 @@ class WhisperModel:
         if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
             raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
         lockstep_fallback = _resolve_lockstep_fallback(lockstep_fallback)
+        captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
+        word_timestamps = captions.pop("word_timestamps", word_timestamps)
 
         def per_file(v, name):
             if isinstance(v, (list, tuple)):
@@ -798,7 +852,7 @@ class WhisperModel:
                 word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, **captions)
 
         files: dict = {}
         results: List[List[Segment]] = [[] for _ in range(n)]
@@ -819,7 +873,7 @@ class WhisperModel:
                 vad_parameters=vad_parameters, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
                 hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hot[f],
                 language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, captions=captions)
             options.lockstep_fallback = lockstep_fallback
             files[f] = [features, info, chunks]
             return SeekState(features.shape[1] - 1, tokenizer, options, self.max_length, self.frames_per_second)
@@ -841,7 +895,7 @@ class WhisperModel:
             if chunks:
                 from .vad import restore_speech_timestamps
                 segments = list(restore_speech_timestamps(iter(segments), chunks, SAMPLE_RATE))
-            out.append((segments, info))
+            out.append((list(_shaped(iter(segments), info.transcription_options)), info))
         return out
 
     # ------------------------------------------------------------------ forced alignment
@@ -982,7 +1036,8 @@ class WhisperModel:
                     timing = alignments[si][wi]
                     if timing["word"]:
                         words.append(dict(word=timing["word"], start=round(time_offset + timing["start"], 2),
-                                          end=round(time_offset + timing["end"], 2), probability=timing["probability"]))
+                                          end=round(time_offset + timing["end"], 2), probability=timing["probability"],
+                                          tokens=timing["tokens"]))
                     saved += len(timing["tokens"])
                     wi += 1
                 if words:
@@ -1198,14 +1253,20 @@ class BatchedInferencePipeline:
                    hallucination_silence_threshold: Optional[float] = None, batch_size: int = 16,
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
                    language_detection_segments: int = 1,
-                   sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None):
-        """sequence_bias: as WhisperModel.transcribe (one table for every window of the file)."""
+                   sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None,
+                   max_line_width: Optional[int] = None, max_line_count: Optional[int] = None,
+                   max_cue_seconds: Optional[float] = None):
+        """sequence_bias: as WhisperModel.transcribe (one table for every window of the file).
+        max_line_width, max_line_count, max_cue_seconds: caption shaping as in WhisperModel.transcribe; the windows
+        then decode as with word_timestamps=True and the segments leave through captions.shape_captions."""
         for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
             if val != default:
                 raise NotImplementedError(f"{name}={val!r} is not supported by the MI355X engine")
         if prefix is not None:       # every window of a batch shares one prompt length; a prefix belongs to the first only
             raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
+        captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
+        word_timestamps = captions.pop("word_timestamps", word_timestamps)
         prep = self._prepare(audio, language, vad_filter, vad_parameters, language_detection_segments,
                              language_detection_threshold)
         tokenizer = self.model.tokenizer(task=task, language=prep["language"])
@@ -1218,7 +1279,7 @@ class BatchedInferencePipeline:
             without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
             append_punctuations=append_punctuations, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
-            sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias))
+            sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias), captions=captions)
         windows = prep["windows"]
         offsets = [s * HOP_LENGTH / SAMPLE_RATE for s, _ in windows]
         results = self.decode_windows(prep["features"], windows, offsets, tokenizer, options, last_speech={})
@@ -1235,10 +1296,15 @@ class BatchedInferencePipeline:
         its own global max, as faster-whisper does per file) and every window keeps its file's time offsets.
         Returns [(segments, info)] per file, in input order; each file's result is what `transcribe` gives for
         it alone (same windows, prompts and options).  sequence_bias (in **kw, see WhisperModel.transcribe) is one
-        mapping for all files; a per-file list raises ValueError."""
+        mapping for all files; a per-file list raises ValueError.  max_line_width, max_line_count, max_cue_seconds
+        (in **kw too): caption shaping as in WhisperModel.transcribe, applied to every file's segments on their own."""
         n = len(audios)
         if kw.pop("prefix", None) is not None:
             raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
+        captions = _caption_options(kw.pop("max_line_width", None), kw.pop("max_line_count", None),
+                                    kw.pop("max_cue_seconds", None))
+        if "word_timestamps" in captions:
+            kw["word_timestamps"] = captions.pop("word_timestamps")
         sequence_bias = kw.pop("sequence_bias", None)
         if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
             raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
@@ -1252,7 +1318,8 @@ class BatchedInferencePipeline:
         for lang in sorted({p["language"] for p in preps}):
             files = [i for i, p in enumerate(preps) if p["language"] == lang]
             tokenizer = self.model.tokenizer(task=task, language=lang)
-            options = self._options(tokenizer, sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias), **kw)
+            options = self._options(tokenizer, sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias),
+                                    captions=captions, **kw)
             feats = torch.cat([preps[i]["features"] for i in files], dim=1) if len(files) > 1 else preps[files[0]]["features"]
             windows, offsets, fids, bases = [], [], [], {}
             base = 0
@@ -1321,8 +1388,10 @@ class BatchedInferencePipeline:
                  prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
                  max_new_tokens: Optional[int] = None, clip_timestamps=None, repetition_penalty: float = 1,
                  no_repeat_ngram_size: int = 0, hotwords: Optional[str] = None,
-                 sequence_bias=(None, None)) -> TranscriptionOptions:
-        """sequence_bias: (the mapping in force, the engine's table), WhisperModel._sequence_bias' pair"""
+                 sequence_bias=(None, None), captions: Optional[dict] = None) -> TranscriptionOptions:
+        """sequence_bias: (the mapping in force, the engine's table), WhisperModel._sequence_bias' pair; captions:
+        _caption_options' dict (word_timestamps is the caller's, set from it already)"""
+        on = captions if captions and captions["max_line_width"] else {}
         temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
         return TranscriptionOptions(
             beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
@@ -1336,7 +1405,9 @@ class BatchedInferencePipeline:
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
             append_punctuations=append_punctuations, multilingual=False, max_new_tokens=max_new_tokens,
             clip_timestamps=clip_timestamps or "0", hallucination_silence_threshold=None, hotwords=hotwords,
-            sequence_bias=sequence_bias[0], sequence_bias_table=sequence_bias[1])
+            sequence_bias=sequence_bias[0], sequence_bias_table=sequence_bias[1],
+            max_line_width=on.get("max_line_width"), max_line_count=on.get("max_line_count"),
+            max_cue_seconds=on.get("max_cue_seconds"))
 
     @staticmethod
     def _info(prep: dict, options: TranscriptionOptions) -> TranscriptionInfo:
@@ -1346,6 +1417,10 @@ class BatchedInferencePipeline:
                                  vad_options=prep["vad_opts"])
 
     def _segments(self, features, results: List[WindowResult], tokenizer: Tokenizer, options: TranscriptionOptions):
+        """The windows' segments in order, ids 1, 2, ...; through captions.shape_captions when the options have it on."""
+        return _shaped(self._window_stream(results, tokenizer, options), options)
+
+    def _window_stream(self, results: List[WindowResult], tokenizer: Tokenizer, options: TranscriptionOptions):
         idx = 0
         for wr in results:
             cur = wr.segments if wr.segments is not None else self.window_segments(wr, tokenizer, options)
@@ -1357,7 +1432,7 @@ class BatchedInferencePipeline:
                 yield Segment(id=idx, seek=wr.seek, start=s["start"], end=s["end"], text=text, tokens=s["tokens"],
                               avg_logprob=wr.avg_logprob, compression_ratio=wr.compression_ratio,
                               no_speech_prob=wr.no_speech_prob, temperature=wr.temperature,
-                              words=[Word(**w) for w in s["words"]] if options.word_timestamps else None)
+                              words=[_word(w) for w in s["words"]] if options.word_timestamps else None)
 
 
 def default_batched_options(**kw) -> dict:
