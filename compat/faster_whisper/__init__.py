@@ -18,6 +18,7 @@ if _ROOT not in sys.path:
 from vlog_amd.audio import load_audio as _load_audio, read_wav as _read_wav, resample_host as _resample_host  # noqa: E402
 from vlog_amd.captions import shape_captions  # noqa: E402,F401
 from vlog_amd.dims import known_models  # noqa: E402
+from vlog_amd.language_id import LanguageWindow  # noqa: E402,F401
 from vlog_amd.transcribe import (  # noqa: E402,F401
     BatchedInferencePipeline,
     Segment,
@@ -65,4 +66,4 @@ def format_timestamp(seconds: float, always_include_hours: bool = False, decimal
 
 __all__ = ["WhisperModel", "BatchedInferencePipeline", "decode_audio", "available_models", "download_model",
            "format_timestamp", "Segment", "Word", "TranscriptionInfo", "TranscriptionOptions", "VadOptions",
-           "shape_captions", "__version__"]
+           "shape_captions", "LanguageWindow", "__version__"]

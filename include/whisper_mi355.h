@@ -312,6 +312,24 @@ int wm_forward(wm_engine* e, int32_t n_seq, const int32_t* h_slots, int32_t seq_
 int wm_detect_language(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t lang_begin, int32_t n_langs,
                        float* h_probs, void* stream);
 
+/* Language identification of n windows (slots h_slots, any order, repeats allowed) in one call, optionally restricted
+ * to a set of candidate languages: one decoder step from <|startoftranscript|> per row, then a language head on the
+ * device that reads only rows lang_begin .. lang_begin + n_langs - 1 of the tied embedding (no [n][n_vocab] logits
+ * buffer is allocated or written).  Per row: the final LayerNorm in f32 rounded to bf16 as the logits GEMM's operand
+ * is, the n_langs dot products (f32 sums of the same bf16 x bf16 products wm_detect_language sums, in another order),
+ * the mask, an f32 softmax over the languages left, and the argmax (the lowest index wins ties).
+ *   h_allowed   [n_langs] bytes or NULL (= all): language j takes part iff h_allowed[j] != 0; the probabilities are
+ *               renormalised over the allowed languages and a masked language's probability is exactly 0.0f.
+ *   h_probs     [n][n_langs] in language-token order; h_top [n] the best language's index (0-based from
+ *               lang_begin); h_top_prob [n] its probability.
+ * Rows are decoded 160 per pass in call order.  The call fails before any launch, naming the argument, when
+ * lang_begin .. lang_begin + n_langs leaves the vocabulary, n_langs is outside 1..128, h_allowed sets no language or
+ * a slot is outside the reserved ones; it fails with "wm_language_id: non-finite logits, row r" when row r has no
+ * finite logit among its allowed languages.  wm_detect_language is unchanged and stays the full-vocabulary form. */
+int wm_language_id(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t lang_begin, int32_t n_langs,
+                   const uint8_t* h_allowed /* [n_langs] or NULL = all */, float* h_probs /* [n][n_langs] */,
+                   int32_t* h_top /* [n] */, float* h_top_prob /* [n] */, void* stream);
+
 /* ctranslate2 Whisper.align(encoder_output, start_sequence, text_tokens, num_frames, median_filter_width)
  * [FW↑] for ONE window (faster-whisper find_alignment, word_timestamps=True): teacher-forced decoder pass over
  * h_sot + <|notimestamps|> + h_text + <|endoftext|> with the n_heads (layer, head) alignment heads'

@@ -24,6 +24,7 @@ SYMBOLS = (
     "wm_cross_kv_fp8_quantize",
     "wm_set_sequence_bias",
     "wm_generate_seeded",
+    "wm_language_id",
 )
 
 
@@ -87,6 +88,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "wm_forward": (C.c_int, [vp, i32, C.POINTER(i32), i32, C.POINTER(i32), vp, i32, C.POINTER(i32), i32, vp, vp]),
         "wm_frame_energy": (C.c_int, [vp, vp, i64, i32, vp, vp]),
         "wm_detect_language": (C.c_int, [vp, i32, C.POINTER(i32), i32, i32, C.POINTER(C.c_float), vp]),
+        "wm_language_id": (C.c_int, [vp, i32, C.POINTER(i32), i32, i32, C.POINTER(C.c_uint8), C.POINTER(C.c_float),
+                                     C.POINTER(i32), C.POINTER(C.c_float), vp]),
         "wm_vad_probs": (C.c_int, [vp, vp, vp, i64, vp, vp, vp]),
         "wm_pcm_from_s16": (C.c_int, [vp, vp, i64, vp, vp]),
         "wm_resample_plan": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),

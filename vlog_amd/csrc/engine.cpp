@@ -877,7 +877,9 @@ void decoder_pass(wm_engine* e, int rows, const int* row_tok, const int* row_pos
                     (split && l == 0 && i == 0) ? e->ev_mid : nullptr);
     }
   }
+  // logits == nullptr (wm_language_id): the pass stops here, the rows' last hidden states (before dec.ln) stay in s_x
   for (const auto& s : sl) {
+    if (!logits) break;
     const int nl = split ? s.rows : n_logit;
     const int* lr = split ? nullptr : logit_rows;
     {
@@ -1886,8 +1888,11 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
 }
 
 // logit_rows (optional): the pass rows whose logits are wanted, in output order (overrides last_only)
+// hidden_only: no final LayerNorm and no logits GEMM (d_logits unused); row s * S + p of e->s_x ([rows][n_state] f32)
+// then holds the last hidden state of sequence s at position p, on `st`, until the next pass
 void forward(wm_engine* e, int n_seq, const int* h_slots, int S, const int* h_tokens, float* d_logits, int last_only,
-             const int* h_align, int n_align, float* d_attn, hipStream_t st, const std::vector<int>* logit_rows = nullptr) {
+             const int* h_align, int n_align, float* d_attn, hipStream_t st, const std::vector<int>* logit_rows = nullptr,
+             bool hidden_only = false) {
   check_weights(e);
   const auto& m = e->dm;
   const int C = m.n_text_ctx, H = m.n_head;
@@ -1935,8 +1940,8 @@ void forward(wm_engine* e, int n_seq, const int* h_slots, int S, const int* h_to
   }
   struct TfReset { wm_engine* e; ~TfReset() { e->tf_nwin = 0; } } tf_reset{e};
   decoder_pass(e, rows, e->d_prow_tok.as<int>(), e->d_prow_pos.as<int>(), e->d_prow_hyp.as<int>(), nullptr,
-               e->d_lin.as<int>(), e->d_logit_rows.as<int>(), nlog, d_logits, n_align ? &amap : nullptr, n_align,
-               n_align ? d_attn : nullptr, S, st);
+               e->d_lin.as<int>(), e->d_logit_rows.as<int>(), nlog, hidden_only ? nullptr : d_logits,
+               n_align ? &amap : nullptr, n_align, n_align ? d_attn : nullptr, S, st);
   HIP_OK(hipStreamSynchronize(st));
 }
 
@@ -2848,6 +2853,67 @@ int wm_detect_language(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t 
     launch_lang_probs(e->a_logits.as<float>(), V, n, lang_begin, n_langs, e->a_probs.as<float>(), st);
     HIP_OK(hipMemcpyAsync(h_probs, e->a_probs.p, (size_t)n * n_langs * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+  });
+}
+
+int wm_language_id(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t lang_begin, int32_t n_langs,
+                   const uint8_t* h_allowed, float* h_probs, int32_t* h_top, float* h_top_prob, void* stream) {
+  return guarded(e, [&] {
+    require_weights(e);
+    if (n < 0) throw std::runtime_error("wm_language_id: n must be >= 0");
+    if (n_langs <= 0 || n_langs > SEARCH_LANG_MAX)
+      throw std::runtime_error("wm_language_id: n_langs outside 1.." + std::to_string(SEARCH_LANG_MAX));
+    if (lang_begin < 0 || lang_begin + n_langs > e->dm.n_vocab)
+      throw std::runtime_error("wm_language_id: lang_begin .. lang_begin + n_langs outside the vocabulary");
+    if (h_allowed && std::none_of(h_allowed, h_allowed + n_langs, [](uint8_t v) { return v != 0; }))
+      throw std::runtime_error("wm_language_id: h_allowed sets no language");
+    if (n == 0) return;
+    if (!h_slots || !h_probs || !h_top || !h_top_prob) throw std::runtime_error("wm_language_id: null argument");
+    for (int i = 0; i < n; ++i)
+      if (h_slots[i] < 0 || h_slots[i] >= e->n_slots)
+        throw std::runtime_error("wm_language_id: h_slots[" + std::to_string(i) + "] outside the reserved slots");
+    hipStream_t st = (hipStream_t)stream;
+    const int d = e->dm.n_state;
+    // rows per decoder pass (the hypothesis tables and the step scratch grow to one pass, not to n)
+    constexpr int PASS = 160;
+    const int cap = std::min(n, PASS);
+    // a pass's results packed in one buffer, [rows][n_langs] probabilities, [rows] best index, [rows] its probability:
+    // one copy back per pass
+    const size_t per_row = (size_t)n_langs + 2;
+    e->a_probs.ensure((size_t)cap * per_row * 4);
+    e->a_meta.ensure((size_t)SEARCH_LANG_MAX);
+    reserve(e, e->n_slots, cap);                             // (also the error word's buffer)
+    int* err = e->d_n_active.as<int>() + 1;
+    HIP_OK(hipMemsetAsync(err, 0, 3 * 4, st));
+    if (h_allowed) HIP_OK(hipMemcpyAsync(e->a_meta.p, h_allowed, n_langs, hipMemcpyHostToDevice, st));
+    const std::vector<int> toks(cap, e->dm.sot);
+    std::vector<float> host((size_t)n * per_row);
+    for (int r0 = 0; r0 < n; r0 += PASS) {
+      const int nr = std::min(PASS, n - r0);
+      forward(e, nr, h_slots + r0, 1, toks.data(), nullptr, 1, nullptr, 0, nullptr, st, nullptr, true);
+      float* d_probs = e->a_probs.as<float>();
+      int* d_top = (int*)(d_probs + (size_t)nr * n_langs);
+      float* d_top_prob = d_probs + (size_t)nr * n_langs + nr;
+      launch_lang_head(e->s_x.as<float>(), d, nr, d, e->Wf("dec.ln.w"), e->Wf("dec.ln.b"), e->Wb("dec.embed"), lang_begin,
+                       n_langs, h_allowed ? e->a_meta.as<unsigned char>() : nullptr, d_probs, d_top, d_top_prob, r0, err, st);
+      HIP_OK(hipMemcpyAsync(host.data() + (size_t)r0 * per_row, d_probs, (size_t)nr * per_row * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));                        // (a later pass reuses a_probs: each copy is ordered before it)
+    bool failed = false;
+    for (int r0 = 0; r0 < n; r0 += PASS) {
+      const int nr = std::min(PASS, n - r0);
+      const float* src = host.data() + (size_t)r0 * per_row;
+      std::memcpy(h_probs + (size_t)r0 * n_langs, src, (size_t)nr * n_langs * 4);
+      std::memcpy(h_top + r0, src + (size_t)nr * n_langs, (size_t)nr * 4);
+      std::memcpy(h_top_prob + r0, src + (size_t)nr * n_langs + nr, (size_t)nr * 4);
+      for (int i = 0; i < nr; ++i) failed |= h_top[r0 + i] < 0;
+    }
+    if (failed) {                                            // a failed row has no best language; the error word names one
+      int h_err[3] = {0, 0, 0};
+      HIP_OK(hipMemcpyAsync(h_err, err, sizeof(h_err), hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+      throw std::runtime_error("wm_language_id: non-finite logits, row " + std::to_string(h_err[1]));
+    }
   });
 }
 

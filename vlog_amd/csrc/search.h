@@ -5,6 +5,7 @@
 #define SEARCH_PER 52            // ids per thread: vocab <= SEARCH_SB * SEARCH_PER = 53248
 #define SEARCH_BIAS_MAX 1024     // sequence-bias table: entries
 #define SEARCH_BIAS_LEN 16       // ... and tokens per entry
+#define SEARCH_LANG_MAX 128      // language head: languages per call (Whisper has 99 or 100)
 
 struct SearchParams {
   const float* logits;   // [rows][V] f32, row r belongs to hypothesis r
@@ -118,6 +119,14 @@ void search_suppress_bits(const unsigned char* sup, int V, unsigned long long* b
 void launch_beam_select(const BeamParams& p, int n_win, hipStream_t st);
 // out[r][j] = softmax(logits row r restricted to [lang_begin, lang_begin + n_langs))[j]
 void launch_lang_probs(const float* logits, long long ldl, int rows, int lang_begin, int n_langs, float* out, hipStream_t st);
+// Language head: row r of x ([rows][ldx] f32, the decoder's last hidden state before dec.ln) -> LayerNorm(g, b) rounded
+// to bf16 -> dot products with rows lang_begin .. lang_begin + n_langs - 1 of E ([V][d] bf16) -> optional mask
+// (allowed[j] == 0: probability exactly 0; nullptr: all) -> f32 softmax probs[r][n_langs], top_id[r] (lowest index on
+// ties), top_prob[r].  A row without a finite allowed logit reports (WM_ERR_NONFINITE, row0 + r) through err.
+// d: 384, 512, 768, 1024 or 1280; n_langs <= SEARCH_LANG_MAX.
+void launch_lang_head(const float* x, long long ldx, int rows, int d, const float* g, const float* b, const bf16* E,
+                      int lang_begin, int n_langs, const unsigned char* allowed, float* probs, int* top_id,
+                      float* top_prob, int row0, int* err, hipStream_t st);
 // out[out_idx ? out_idx[r] : r] = softmax(logits row r)[no_speech]
 void launch_no_speech(const float* logits, long long ldl, int V, int rows, int no_speech, float* out, hipStream_t st,
                       const int* out_idx = nullptr);

@@ -928,6 +928,176 @@ void launch_lang_probs(const float* logits, long long ldl, int rows, int lang_be
   WM_LAUNCH_CHECK("lang_probs_kernel");
 }
 
+// Language head (wm_language_id): the language tokens' probabilities straight from the decoder's last hidden state,
+// without the full-vocabulary logits.  One 256-thread workgroup per row, fused:
+//   1. the final LayerNorm (dec.ln) in f32 with layernorm_kernel's statistics (norm.hip: one wave, lane l owns the
+//      float2 pairs l + 64 i, the same sums in the same order; each of the four waves repeats them, so no block-wide
+//      step is needed), rounded to bf16 as the logits GEMM's operand is, into LDS;
+//   2. the dot products with rows lang_begin .. lang_begin + n_langs - 1 of the tied embedding: wave w takes languages
+//      w, w + 4, ...; a lane owns the 16-B chunks lane + 64 s of a row (NS = ceil(D / 512) of them; D = 384 leaves lanes
+//      48..63 idle, D = 1280 lanes 32..63 of the last step) and keeps its chunks of the normalised state in registers.
+//      The loads of LB languages are issued together before the first use (NS * LB 16-B loads in flight per lane), then
+//      each language's partial is summed over the wave.  Every product bf16 x bf16 is exact in f32, so the logit is an
+//      f32 sum of the products the full-vocabulary GEMM sums, in another order;
+//   3. the allowed mask (allowed[j] == 0: logit -inf, probability exactly 0); an allowed logit that is not finite
+//      counts as masked, and a row that keeps no language is an error (err: WM_ERR_NONFINITE, the row);
+//   4. the f32 softmax of lang_probs_kernel (f32 max and sum over the block, expf(x - max) / sum);
+//   5. the argmax, the lowest index winning ties (block_argmax's rule).
+// Nothing in a row's arithmetic depends on the other rows or on the grid.
+#define LANG_MAX SEARCH_LANG_MAX
+#define LANG_LB 8               // languages whose loads a wave issues together
+// block_argmax for a 256-thread block (four waves): the same rule and order
+__device__ Cand block_argmax_4(Cand c, Cand* sh) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(c.v, o, 64);
+    const int i2 = __shfl_xor(c.i, o, 64);
+    if (better(v2, i2, c.v, c.i)) { c.v = v2; c.i = i2; }
+  }
+  if (lane == 0) sh[wv] = c;
+  __syncthreads();
+  Cand r = sh[0];
+  for (int w = 1; w < 4; ++w)
+    if (better(sh[w].v, sh[w].i, r.v, r.i)) r = sh[w];
+  return r;
+}
+template <int D>
+__global__ __launch_bounds__(256) void lang_head_kernel(const float* __restrict__ x, long long ldx,
+                                                        const float* __restrict__ g, const float* __restrict__ b,
+                                                        const bf16* __restrict__ E, int lang_begin, int n_langs,
+                                                        const unsigned char* __restrict__ allowed, float eps,
+                                                        float* __restrict__ probs, int* __restrict__ top_id,
+                                                        float* __restrict__ top_prob, int row0, int* __restrict__ err) {
+  constexpr int NP = D / 128;                 // float2 pairs per lane (layernorm_kernel<NP>)
+  constexpr int NC = D / 8;                   // 16-B chunks per embedding row
+  constexpr int NS = (NC + 63) / 64;          // chunks per lane
+  __shared__ __attribute__((aligned(16))) bf16 s_h[D];
+  __shared__ float s_lg[LANG_MAX];
+  __shared__ float sh[4];
+  __shared__ Cand sh_c[4];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // 1. LayerNorm: every wave computes the row's statistics as layernorm_kernel's one wave does
+  {
+    const float2* xr = (const float2*)(x + (long long)row * ldx);
+    float2 v[NP];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      v[i] = xr[lane + 64 * i];
+      s += v[i].x + v[i].y;
+    }
+    const float mean = wave_sum(s) * (1.0f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const float a = v[i].x - mean, c = v[i].y - mean;
+      q += a * a + c * c;
+    }
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+    const float2* g2 = (const float2*)g;
+    const float2* b2 = (const float2*)b;
+    bf16x2* hr = (bf16x2*)s_h;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      if ((i & 3) != wv) continue;            // the waves hold the same values: each stores a quarter of the pairs
+      const int c = lane + 64 * i;
+      const float2 gg = g2[c], bb = b2[c];
+      bf16x2 o;
+      o[0] = f2bf((v[i].x - mean) * rstd * gg.x + bb.x);
+      o[1] = f2bf((v[i].y - mean) * rstd * gg.y + bb.y);
+      hr[c] = o;
+    }
+  }
+  __syncthreads();
+  // 2. language logits
+  bf16x8 h[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const int c = lane + 64 * s;
+    h[s] = ((const bf16x8*)s_h)[c < NC ? c : 0];
+  }
+  const bf16x8* Er = (const bf16x8*)(E + (long long)lang_begin * D);
+  for (int j0 = wv; j0 < n_langs; j0 += 4 * LANG_LB) {
+    bf16x8 w[LANG_LB][NS];
+#pragma unroll
+    for (int k = 0; k < LANG_LB; ++k) {
+      const int j = min(j0 + 4 * k, n_langs - 1);        // clamped: the load count is static, the extra sums are dropped
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int c = lane + 64 * s;
+        w[k][s] = Er[(long long)j * NC + (c < NC ? c : 0)];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < LANG_LB; ++k) {
+      float acc = 0.f;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (lane + 64 * s < NC) {
+#pragma unroll
+          for (int t = 0; t < 8; ++t) acc = fmaf(bf2f(h[s][t]), bf2f(w[k][s][t]), acc);
+        }
+      }
+      acc = wave_sum(acc);
+      const int j = j0 + 4 * k;
+      if (lane == 0 && j < n_langs) s_lg[j] = acc;
+    }
+  }
+  __syncthreads();
+  // 3. mask, 4. softmax, 5. argmax (n_langs <= LANG_MAX < 256: one language per thread)
+  float lg = -INFINITY;
+  if (tid < n_langs) {
+    const float v = s_lg[tid];
+    if ((!allowed || allowed[tid]) && isfinite(v)) lg = v;
+  }
+  Cand best = block_argmax_4(Cand{lg, tid < n_langs ? tid : 0x7fffffff}, sh_c);
+  const float m = best.v;
+  if (!(m > -INFINITY)) {                                  // no allowed language with a finite logit
+    if (tid == 0) {
+      wm_report_error(err, WM_ERR_NONFINITE, row0 + row, 0);
+      top_id[row] = -1;
+      top_prob[row] = 0.f;
+    }
+    if (tid < n_langs) probs[(long long)row * n_langs + tid] = 0.f;
+    return;
+  }
+  float s = tid < n_langs ? expf(lg - m) : 0.f;
+  s = wave_sum(s);
+  if (lane == 0) sh[wv] = s;
+  __syncthreads();
+  s = sh[0] + sh[1] + sh[2] + sh[3];
+  const float p = expf(lg - m) / s;                        // masked: expf(-inf) = 0, exactly 0 / s
+  if (tid < n_langs) probs[(long long)row * n_langs + tid] = p;
+  if (tid == best.i) {
+    top_id[row] = tid;
+    top_prob[row] = p;
+  }
+}
+
+void launch_lang_head(const float* x, long long ldx, int rows, int d, const float* g, const float* b, const bf16* E,
+                      int lang_begin, int n_langs, const unsigned char* allowed, float* probs, int* top_id,
+                      float* top_prob, int row0, int* err, hipStream_t st) {
+  if (rows <= 0) return;
+  if (n_langs <= 0 || n_langs > LANG_MAX) throw std::runtime_error("lang_head: n_langs outside 1.." + std::to_string(LANG_MAX));
+  if (ldx % 2 != 0) throw std::runtime_error("lang_head: odd row stride");
+  const float eps = 1e-5f;
+  const dim3 grid(rows), block(256);
+#define LANG_HEAD(DD)                                                                                              \
+  hipLaunchKernelGGL(lang_head_kernel<DD>, grid, block, 0, st, x, ldx, g, b, E, lang_begin, n_langs, allowed, eps, \
+                     probs, top_id, top_prob, row0, err)
+  switch (d) {
+    case 384: LANG_HEAD(384); break;
+    case 512: LANG_HEAD(512); break;
+    case 768: LANG_HEAD(768); break;
+    case 1024: LANG_HEAD(1024); break;
+    case 1280: LANG_HEAD(1280); break;
+    default: throw std::runtime_error("lang_head: unsupported width " + std::to_string(d));
+  }
+#undef LANG_HEAD
+  WM_LAUNCH_CHECK("lang_head_kernel");
+}
+
 // softmax(logits[r])[no_speech]
 __global__ __launch_bounds__(SB) void no_speech_kernel(const float* __restrict__ logits, long long ldl, int V, int ns,
                                                         float* __restrict__ out, const int* __restrict__ out_idx) {

@@ -515,6 +515,28 @@ class GpuEngine:
                                                     self.stream_ptr()), "wm_detect_language")
         return probs
 
+    def language_id(self, slots: Sequence[int], lang_begin: int, n_langs: int,
+                    allowed: Optional[Sequence[int]] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """wm_language_id: one decoder step from <|startoftranscript|> per slot and the language head on the device
+        (no full-vocabulary logits).  `allowed` ([n_langs] of 0 / 1, None = all) restricts the softmax; a masked
+        language's probability is exactly 0.  -> (probs [n, n_langs] f32, top [n] i32, top_prob [n] f32)."""
+        h_slots = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(h_slots)
+        probs = np.zeros((n, max(n_langs, 0)), dtype=np.float32)
+        top = np.zeros(n, dtype=np.int32)
+        top_prob = np.zeros(n, dtype=np.float32)
+        mask = None
+        if allowed is not None:
+            mask = np.ascontiguousarray(np.asarray(allowed) != 0, dtype=np.uint8)
+            if mask.shape != (n_langs,):
+                raise ValueError(f"language_id: allowed must have n_langs = {n_langs} entries, got {mask.shape}")
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.wm_language_id(self.h, n, _i32p(h_slots), lang_begin, n_langs,
+                                                mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None,
+                                                _f32p(probs), _i32p(top), _f32p(top_prob), self.stream_ptr()),
+                        "wm_language_id")
+        return probs, top, top_prob
+
     def align(self, slot: int, sot_sequence: Sequence[int], text_tokens: Sequence[int], num_frames: int,
               alignment_heads: Sequence[Tuple[int, int]], median_filter_width: int = 7):
         """-> (text_token_probs [n_text], text_indices, time_indices) (CTranslate2 Whisper.align for one window)."""

@@ -37,6 +37,8 @@ from . import segments as segs
 from .segments import _word_means, merge_punctuations
 from .audio import mono_f32, read_wav
 from .captions import resolve_caption_options, set_word_tokens, shape_captions
+from .language_id import (LanguageWindow, candidate_mask, candidates_in_force, detection_rule, detection_windows,
+                          timeline_windows, window_probs, window_times)
 from .seek_state import (ENERGY_FRAME_MEL, MAX_SECTIONS, SeekState, chunk_joins, decode_round_levels, decode_round_with,
                          fallback_ladder, iter_lockstep, plan_sections, run_lockstep, window_max_length)
 from .dims import CHUNK_LENGTH, HOP_LENGTH, N_FRAMES, SAMPLE_RATE, TIME_PRECISION
@@ -115,6 +117,7 @@ class TranscriptionOptions:
     max_line_width: Optional[int] = None        # caption shaping (captions.shape_captions) as in force; None: off.
     max_line_count: Optional[int] = None        # ... while it is on, word_timestamps reads True
     max_cue_seconds: Optional[float] = None
+    language_candidates: Optional[Tuple[str, ...]] = None      # the language whitelist in force (None: off)
 
 
 @dataclass
@@ -287,6 +290,13 @@ class WhisperModel:
     def tokenizer(self, task: Optional[str] = "transcribe", language: Optional[str] = None) -> Tokenizer:
         return Tokenizer(self.dims, task=task, language=language, tokenizer_json=self._tokenizer_json, seed=self._tok_seed)
 
+    def _language_candidates(self, value, language: Optional[str] = None) -> Optional[Tuple[str, ...]]:
+        """The `language_candidates` argument of a call -> the tuple in force, or None (language_id.py): None reads
+        VLOG_AMD_LANGUAGE_CANDIDATES, an empty sequence is off; ignored when the call names its language and in an
+        English-only model."""
+        codes = self.dims.specials.lang_codes if self.is_multilingual else ()
+        return candidates_in_force(value, os.environ, codes, self.is_multilingual, language)
+
     def _sequence_bias(self, tokenizer: Tokenizer, sequence_bias):
         """The `sequence_bias` argument of a transcribe call -> (the mapping in force, the engine's table or None).
         None takes the VLOG_AMD_SEQUENCE_BIAS file's mapping when there is one; anything but a mapping (a per-file
@@ -332,12 +342,32 @@ class WhisperModel:
     # ------------------------------------------------------------------ language detection
     def detect_language(self, audio: Optional[np.ndarray] = None, features: Optional[torch.Tensor] = None,
                         vad_filter: bool = False, vad_parameters=None, language_detection_segments: int = 1,
-                        language_detection_threshold: float = 0.5) -> Tuple[str, float, List[Tuple[str, float]]]:
+                        language_detection_threshold: float = 0.5,
+                        language_candidates: Optional[Sequence[str]] = None) -> Tuple[str, float, List[Tuple[str, float]]]:
         """faster-whisper `detect_language`: encode up to `language_detection_segments` windows, one decoder
         step from <|startoftranscript|>, softmax over the language tokens; majority vote if no window is
-        confident."""
+        confident.
+
+        language_candidates (see `transcribe`): with candidates in force the windows are encoded in ONE encode call
+        and identified in ONE wm_language_id call with the candidates' mask; the rule above is then applied on the
+        host to the per-window results in window order (language_id.detection_rule), and the probabilities returned
+        are over the candidates only.  Off (and VLOG_AMD_LANGUAGE_CANDIDATES unset): the loop below, untouched."""
+        candidates = self._language_candidates(language_candidates)
         if not self.is_multilingual:
             return "en", 1.0, [("en", 1.0)]
+        if candidates is not None:
+            st = self.dims.specials
+            with self._lock:
+                if features is None:
+                    features = self._features(audio)
+                content = features.shape[1] - 1 if features.shape[1] > 1 else features.shape[1]
+                wins = detection_windows(content, language_detection_segments)
+                enc = self.engine.encode(features, [s for s, _ in wins], [n for _, n in wins])
+                self.engine.cross_kv(enc, 0)
+                probs, _, _ = self.engine.language_id(list(range(len(wins))), st.lang_begin, st.n_langs,
+                                                      candidate_mask(candidates, st.lang_codes))
+            return detection_rule([window_probs(p, st.lang_codes, candidates) for p in probs],
+                                  language_detection_threshold)
         with self._lock:
             if features is None:
                 features = self._features(audio)
@@ -365,6 +395,54 @@ class WhisperModel:
                 prob = max(info[lang])
             return lang, prob, all_probs
 
+    def language_timeline(self, audio: Union[str, BinaryIO, np.ndarray], vad_filter: bool = False, vad_parameters=None,
+                          language_candidates: Optional[Sequence[str]] = None,
+                          max_windows: Optional[int] = None) -> List[LanguageWindow]:
+        """Which language is spoken where: one LanguageWindow(start, end, language, probability, probs) per
+        consecutive 30 s window of the audio (of the VAD-collected audio with vad_filter=True; start and end are then
+        moved back to file time with restore_speech_timestamps' arithmetic), at most max_windows of them.  Nothing is
+        decoded: the windows are encoded max_batch_windows at a time, as the throughput pipeline encodes them, with one
+        wm_language_id call per batch; the model lock is held per batch.  language_candidates as in `transcribe`
+        (None reads VLOG_AMD_LANGUAGE_CANDIDATES); `probs` is (code, p) over the languages in force, in
+        language-token order.  ValueError in an English-only model."""
+        if not self.is_multilingual:
+            raise ValueError("language_timeline needs a multilingual model (this one is English-only)")
+        candidates = self._language_candidates(language_candidates)
+        if max_windows is not None and max_windows < 1:
+            raise ValueError("max_windows must be >= 1")
+        if not isinstance(audio, np.ndarray):
+            audio = self._load_audio(audio)
+        audio = np.asarray(audio, dtype=np.float32)
+        speech_chunks = None
+        if vad_filter:
+            from .vad import collect_chunks, get_speech_timestamps
+            vad_opts = vad_parameters if isinstance(vad_parameters, VadOptions) else VadOptions(**(vad_parameters or {}))
+            speech_chunks = get_speech_timestamps(audio, vad_opts, self)
+            if not speech_chunks:
+                return []
+            audio = collect_chunks(audio, speech_chunks)
+        with self._lock:
+            features = self._features(audio)
+        st = self.dims.specials
+        wins = timeline_windows(features.shape[1] - 1, max_windows)
+        times = window_times(wins, speech_chunks)
+        mask = candidate_mask(candidates, st.lang_codes) if candidates is not None else None
+        keep = [j for j in range(st.n_langs) if mask is None or mask[j]]
+        batch = max(1, self._pipeline().max_batch_windows)
+        out: List[LanguageWindow] = []
+        for b0 in range(0, len(wins), batch):
+            part = wins[b0: b0 + batch]
+            with self._lock:
+                enc = self.engine.encode(features, [s for s, _ in part], [n for _, n in part])
+                self.engine.cross_kv(enc, 0)
+                probs, top, top_prob = self.engine.language_id(list(range(len(part))), st.lang_begin, st.n_langs, mask)
+            for i in range(len(part)):
+                start, end = times[b0 + i]
+                out.append(LanguageWindow(start=start, end=end, language=st.lang_codes[int(top[i])],
+                                          probability=float(top_prob[i]),
+                                          probs=tuple((st.lang_codes[j], float(probs[i, j])) for j in keep)))
+        return out
+
     # ------------------------------------------------------------------ transcribe
     def transcribe(self, audio: Union[str, BinaryIO, np.ndarray], language: Optional[str] = None,
                    task: str = "transcribe", log_progress: bool = False, beam_size: int = 5, best_of: int = 5,
@@ -385,8 +463,22 @@ class WhisperModel:
                    sections_in_flight: Optional[int] = None,
                    sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None,
                    lockstep_fallback: Optional[bool] = None, max_line_width: Optional[int] = None,
-                   max_line_count: Optional[int] = None, max_cue_seconds: Optional[float] = None):
+                   max_line_count: Optional[int] = None, max_cue_seconds: Optional[float] = None,
+                   language_candidates: Optional[Sequence[str]] = None):
         """faster-whisper's `WhisperModel.transcribe`, plus these arguments of this engine:
+
+        language_candidates: the language codes this deployment serves, e.g. ["en", "es", "de"].  Used only when
+        `language` is None and the model is multilingual (otherwise ignored; the English-only case is logged once):
+        language detection then runs through wm_language_id with the candidates' mask, so the language chosen is
+        one of them, and info.language_probability / info.all_language_probs are over the candidates only (they sum
+        to 1, sorted descending): the model's probabilities conditioned on the language being a candidate.  The
+        language_detection_segments windows are encoded in one call and identified in one call; faster-whisper's
+        rule (the first window above language_detection_threshold, else the majority of the windows' tops) is
+        applied to the per-window results in window order.  None reads VLOG_AMD_LANGUAGE_CANDIDATES
+        (comma-separated codes); an empty sequence turns it off whatever the environment says.  An unknown code, a
+        duplicate or a malformed variable raises ValueError at the call.  The tuple in force is echoed in
+        info.transcription_options.language_candidates (None when off).  WhisperModel.language_timeline reports the
+        language per 30 s window without decoding anything.
 
         max_line_width, max_line_count, max_cue_seconds: caption shaping (vlog_amd/captions.py).  With a width > 0 the
         call decodes exactly as the same call with word_timestamps=True (the shaper needs word times; they move the
@@ -461,6 +553,7 @@ class WhisperModel:
         lockstep_fallback = _resolve_lockstep_fallback(lockstep_fallback)
         captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
         word_timestamps = captions.pop("word_timestamps", word_timestamps)
+        language_candidates = self._language_candidates(language_candidates, language) or ()
         if self.throughput:
             # opt-in throughput mode for the UNCHANGED worker (VLOG_AMD_THROUGHPUT=1): its call
             # transcribe(wav, language, task, beam_size=5, vad_filter=True) runs as BatchedInferencePipeline:
@@ -478,7 +571,8 @@ class WhisperModel:
                 word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, **captions)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias,
+                language_candidates=language_candidates, **captions)
         if sections > 1 and not isinstance(audio, np.ndarray):
             audio = self._load_audio(audio)     # (the cuts without VAD are chosen on the samples)
         features, tokenizer, options, info, speech_chunks = self._prepare_file(
@@ -495,7 +589,8 @@ class WhisperModel:
             max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
             hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hotwords,
             language_detection_threshold=language_detection_threshold,
-            language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, captions=captions)
+            language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, captions=captions,
+            language_candidates=language_candidates)
         options.lockstep_fallback = lockstep_fallback
         bounds = self._plan_sections(audio, features, speech_chunks, sections) if sections > 1 else None
         if bounds is not None:
@@ -528,10 +623,13 @@ class WhisperModel:
                       prefix, suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp,
                       word_timestamps, prepend_punctuations, append_punctuations, multilingual, vad_filter,
                       vad_parameters, max_new_tokens, clip_timestamps, hallucination_silence_threshold, hotwords,
-                      language_detection_threshold, language_detection_segments, sequence_bias=None, captions=None):
+                      language_detection_threshold, language_detection_segments, sequence_bias=None, captions=None,
+                      language_candidates=()):
         """What `transcribe` does for one file before its seek loop: load, VAD, log-mel, language, tokenizer, options.
-        captions: _caption_options' dict (the caller has word_timestamps from it already).
+        captions: _caption_options' dict (the caller has word_timestamps from it already).  language_candidates: the
+        call's argument (the callers pass what they resolved, () when off); in force for a file without a language.
         -> (features, tokenizer, options, info, speech_chunks)"""
+        candidates = self._language_candidates(language_candidates, language)
         if not isinstance(audio, np.ndarray):
             audio = self._load_audio(audio)
         audio = np.asarray(audio, dtype=np.float32)
@@ -555,7 +653,8 @@ class WhisperModel:
             else:
                 language, language_probability, all_language_probs = self.detect_language(
                     features=features, language_detection_segments=language_detection_segments,
-                    language_detection_threshold=language_detection_threshold or 0.5)
+                    language_detection_threshold=language_detection_threshold or 0.5,
+                    language_candidates=candidates or ())
         else:
             if not self.is_multilingual and language != "en":
                 logger.warning("English-only model used with language=%s; using 'en'", language)
@@ -576,7 +675,7 @@ class WhisperModel:
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
             append_punctuations=append_punctuations, multilingual=multilingual, max_new_tokens=max_new_tokens,
             clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
-            hotwords=hotwords, sequence_bias=bias_map, sequence_bias_table=bias_table)
+            hotwords=hotwords, sequence_bias=bias_map, sequence_bias_table=bias_table, language_candidates=candidates)
         if captions and captions["max_line_width"]:
             options.max_line_width, options.max_line_count = captions["max_line_width"], captions["max_line_count"]
             options.max_cue_seconds = captions["max_cue_seconds"]
@@ -782,7 +881,8 @@ class WhisperModel:
                         max_files: int = 16,
                         sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None,
                         lockstep_fallback: Optional[bool] = None, max_line_width: Optional[int] = None,
-                        max_line_count: Optional[int] = None, max_cue_seconds: Optional[float] = None):
+                        max_line_count: Optional[int] = None, max_cue_seconds: Optional[float] = None,
+                        language_candidates: Optional[Sequence[str]] = None):
         """`transcribe` for several files at once in the sequential (parity) mode -> [(list_of_segments, info)] in
         input order; each file gets what `transcribe(file, same arguments)` gives for it alone.
 
@@ -809,6 +909,8 @@ class WhisperModel:
         each file then gets what `transcribe` gives for it alone to f32 rounding, not bit for bit.
         max_line_width, max_line_count, max_cue_seconds (see `transcribe`): caption shaping, applied to every file's
         segments on their own (ids 1, 2, ... per file).
+        language_candidates (see `transcribe`): ONE sequence of codes for all files, in force for every file whose
+        language is None; a per-file list of lists raises ValueError.
         With throughput mode on, this is BatchedInferencePipeline.transcribe_many."""
         for name, val, default in (("multilingual", multilingual, False),
                                    ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
@@ -826,6 +928,7 @@ class WhisperModel:
         lockstep_fallback = _resolve_lockstep_fallback(lockstep_fallback)
         captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
         word_timestamps = captions.pop("word_timestamps", word_timestamps)
+        language_candidates = self._language_candidates(language_candidates) or ()
 
         def per_file(v, name):
             if isinstance(v, (list, tuple)):
@@ -852,7 +955,8 @@ class WhisperModel:
                 word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, **captions)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias,
+                language_candidates=language_candidates, **captions)
 
         files: dict = {}
         results: List[List[Segment]] = [[] for _ in range(n)]
@@ -873,7 +977,8 @@ class WhisperModel:
                 vad_parameters=vad_parameters, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
                 hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hot[f],
                 language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, captions=captions)
+                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, captions=captions,
+                language_candidates=language_candidates)
             options.lockstep_fallback = lockstep_fallback
             files[f] = [features, info, chunks]
             return SeekState(features.shape[1] - 1, tokenizer, options, self.max_length, self.frames_per_second)
@@ -1255,8 +1360,9 @@ class BatchedInferencePipeline:
                    language_detection_segments: int = 1,
                    sequence_bias: Optional[Mapping[Union[str, Tuple[int, ...]], float]] = None,
                    max_line_width: Optional[int] = None, max_line_count: Optional[int] = None,
-                   max_cue_seconds: Optional[float] = None):
+                   max_cue_seconds: Optional[float] = None, language_candidates: Optional[Sequence[str]] = None):
         """sequence_bias: as WhisperModel.transcribe (one table for every window of the file).
+        language_candidates: as WhisperModel.transcribe (the whitelist of the file's language detection).
         max_line_width, max_line_count, max_cue_seconds: caption shaping as in WhisperModel.transcribe; the windows
         then decode as with word_timestamps=True and the segments leave through captions.shape_captions."""
         for name, val, default in (("multilingual", multilingual, False),
@@ -1267,8 +1373,9 @@ class BatchedInferencePipeline:
             raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
         captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
         word_timestamps = captions.pop("word_timestamps", word_timestamps)
+        language_candidates = self.model._language_candidates(language_candidates, language) or ()
         prep = self._prepare(audio, language, vad_filter, vad_parameters, language_detection_segments,
-                             language_detection_threshold)
+                             language_detection_threshold, language_candidates)
         tokenizer = self.model.tokenizer(task=task, language=prep["language"])
         options = self._options(
             tokenizer, beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
@@ -1279,7 +1386,8 @@ class BatchedInferencePipeline:
             without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
             append_punctuations=append_punctuations, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
-            sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias), captions=captions)
+            sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias), captions=captions,
+            language_candidates=prep["language_candidates"])
         windows = prep["windows"]
         offsets = [s * HOP_LENGTH / SAMPLE_RATE for s, _ in windows]
         results = self.decode_windows(prep["features"], windows, offsets, tokenizer, options, last_speech={})
@@ -1297,7 +1405,8 @@ class BatchedInferencePipeline:
         Returns [(segments, info)] per file, in input order; each file's result is what `transcribe` gives for
         it alone (same windows, prompts and options).  sequence_bias (in **kw, see WhisperModel.transcribe) is one
         mapping for all files; a per-file list raises ValueError.  max_line_width, max_line_count, max_cue_seconds
-        (in **kw too): caption shaping as in WhisperModel.transcribe, applied to every file's segments on their own."""
+        (in **kw too): caption shaping as in WhisperModel.transcribe, applied to every file's segments on their own.
+        language_candidates (in **kw): one sequence of codes for all files, as WhisperModel.transcribe_many."""
         n = len(audios)
         if kw.pop("prefix", None) is not None:
             raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
@@ -1308,11 +1417,12 @@ class BatchedInferencePipeline:
         sequence_bias = kw.pop("sequence_bias", None)
         if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
             raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
+        language_candidates = self.model._language_candidates(kw.pop("language_candidates", None)) or ()
         langs = list(language) if isinstance(language, (list, tuple)) else [language] * n
         if len(langs) != n:
             raise ValueError("one language per file")
         preps = [self._prepare(a, l, vad_filter, vad_parameters, language_detection_segments,
-                               language_detection_threshold) for a, l in zip(audios, langs)]
+                               language_detection_threshold, language_candidates) for a, l in zip(audios, langs)]
         out: List[Optional[tuple]] = [None] * n
         last_speech: dict = {}
         for lang in sorted({p["language"] for p in preps}):
@@ -1320,6 +1430,10 @@ class BatchedInferencePipeline:
             tokenizer = self.model.tokenizer(task=task, language=lang)
             options = self._options(tokenizer, sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias),
                                     captions=captions, **kw)
+            # (the options are one object per language group: they echo the call's whitelist when any file of the
+            # group had its language detected under it)
+            options.language_candidates = next((preps[i]["language_candidates"] for i in files
+                                                if preps[i]["language_candidates"]), None)
             feats = torch.cat([preps[i]["features"] for i in files], dim=1) if len(files) > 1 else preps[files[0]]["features"]
             windows, offsets, fids, bases = [], [], [], {}
             base = 0
@@ -1338,11 +1452,13 @@ class BatchedInferencePipeline:
         return out
 
     def _prepare(self, audio, language, vad_filter, vad_parameters, language_detection_segments,
-                 language_detection_threshold) -> dict:
+                 language_detection_threshold, language_candidates=()) -> dict:
         """One file: PCM, log-mel, its windows (VAD-bounded or fixed) and its language.  `audio` may be an
-        IngestResult (vlog_amd/ingest.py: PCM and log-mel already on the device, computed while streaming)."""
+        IngestResult (vlog_amd/ingest.py: PCM and log-mel already on the device, computed while streaming).
+        language_candidates: the call's resolved whitelist (() = off), in force when the file has no language."""
         from .ingest import IngestResult
         m = self.model
+        candidates = m._language_candidates(language_candidates, language)
         if isinstance(audio, IngestResult):
             features, duration = audio.features, audio.duration
             audio = audio.pcm
@@ -1369,14 +1485,15 @@ class BatchedInferencePipeline:
             if m.is_multilingual and windows:
                 language, language_probability, all_language_probs = m.detect_language(
                     features=features, language_detection_segments=language_detection_segments,
-                    language_detection_threshold=language_detection_threshold or 0.5)
+                    language_detection_threshold=language_detection_threshold or 0.5,
+                    language_candidates=candidates or ())
             else:
                 language, language_probability = "en", 1.0
         else:
             language_probability = 1.0
         return dict(features=features, windows=windows, duration=duration, duration_after_vad=duration_after_vad,
                     vad_opts=vad_opts, language=language, language_probability=language_probability,
-                    all_language_probs=all_language_probs)
+                    all_language_probs=all_language_probs, language_candidates=candidates)
 
     @staticmethod
     def _options(tokenizer: Tokenizer, beam_size: int = 5, best_of: int = 5, patience: float = 1,
@@ -1388,7 +1505,8 @@ class BatchedInferencePipeline:
                  prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
                  max_new_tokens: Optional[int] = None, clip_timestamps=None, repetition_penalty: float = 1,
                  no_repeat_ngram_size: int = 0, hotwords: Optional[str] = None,
-                 sequence_bias=(None, None), captions: Optional[dict] = None) -> TranscriptionOptions:
+                 sequence_bias=(None, None), captions: Optional[dict] = None,
+                 language_candidates: Optional[Tuple[str, ...]] = None) -> TranscriptionOptions:
         """sequence_bias: (the mapping in force, the engine's table), WhisperModel._sequence_bias' pair; captions:
         _caption_options' dict (word_timestamps is the caller's, set from it already)"""
         on = captions if captions and captions["max_line_width"] else {}
@@ -1407,7 +1525,7 @@ class BatchedInferencePipeline:
             clip_timestamps=clip_timestamps or "0", hallucination_silence_threshold=None, hotwords=hotwords,
             sequence_bias=sequence_bias[0], sequence_bias_table=sequence_bias[1],
             max_line_width=on.get("max_line_width"), max_line_count=on.get("max_line_count"),
-            max_cue_seconds=on.get("max_cue_seconds"))
+            max_cue_seconds=on.get("max_cue_seconds"), language_candidates=language_candidates or None)
 
     @staticmethod
     def _info(prep: dict, options: TranscriptionOptions) -> TranscriptionInfo:
