@@ -330,6 +330,45 @@ int wm_language_id(wm_engine* e, int32_t n, const int32_t* h_slots, int32_t lang
                    const uint8_t* h_allowed /* [n_langs] or NULL = all */, float* h_probs /* [n][n_langs] */,
                    int32_t* h_top /* [n] */, float* h_top_prob /* [n] */, void* stream);
 
+/* wm_generate_seeded whose windows choose their own language on the device (faster-whisper's multilingual=True: every
+ * 30 s window is decoded under the language detected for it).  The "auto" windows are those with h_lang_pos[w] >= 0,
+ * in call order.  Before the first prefill they are identified exactly as wm_language_id identifies that sub-list of
+ * slots (160 rows per pass in call order, the same decoder step and language head, the one mask h_allowed for the
+ * whole call), so h_lang, h_lang_prob and h_probs carry the bits of that call.  The best indices stay on the device,
+ * and a kernel (lang_assign_kernel) writes the token lang_begin + h_lang[w] at position h_lang_pos[w] of window w's
+ * prompt in every device table that holds it (each hypothesis' token row and the prefill rows; the row-set forms'
+ * per-window prompt table and, at a refill, the starting windows' pass rows), ordered on the stream after those
+ * tables' uploads and before the pass that prefills them.  Every window is identified at the start of the call, the
+ * row-set forms' later windows too (their cross K/V is in its slot already).  No host wait is added between the
+ * detection and the prefill: the results' copy back is queued behind the language head and is delivered when the call
+ * returns.  From the assignment on the call is wm_generate_seeded with host prompts that hold those tokens: tokens,
+ * scores, cum_logprob, no-speech, the per-step records, h_steps and h_stats are bit-identical to it for the same
+ * windows, order and options, in every decode form (greedy, sampling with any num_hypotheses, with or without seeds,
+ * beam search, ragged prompts, the row-set forms with max_rows below the windows and with compact).
+ *   h_lang_pos   [n_windows]: the prompt position whose token the engine replaces; -1: the window keeps its prompt.
+ *                The host puts a placeholder language token there, right behind <|startoftranscript|>.
+ *   h_lang       out [n_windows]: the chosen index from lang_begin; -1 where h_lang_pos is -1
+ *   h_lang_prob  out [n_windows]: its probability; 0 where h_lang_pos is -1
+ *   h_probs      out [n_windows][n_langs] or NULL; zeros where h_lang_pos is -1
+ * la == NULL is exactly wm_generate_seeded(e, a, h_seeds, stream).  The call fails before any launch, naming the
+ * window, when h_lang_pos[w] is at or beyond that window's prompt length, the token there is not a language token in
+ * [lang_begin, lang_begin + n_langs), or the token before it is not <|startoftranscript|>; and, as wm_language_id,
+ * when n_langs is outside 1..128, the language tokens leave the vocabulary or h_allowed sets no language.  A window
+ * without a finite allowed language logit fails the call ("non-finite language logits, window w") after the decode;
+ * its prompt kept the placeholder.  The engine stays usable after a refusal, and an engine that never makes this call
+ * launches exactly what it launched before.  (Added without an ABI bump: a new entry point, wm_generate_args
+ * unchanged.) */
+typedef struct wm_language_auto {
+  int32_t lang_begin, n_langs;      /* as wm_language_id */
+  const uint8_t* h_allowed;         /* [n_langs] or NULL = all (one mask per call) */
+  const int32_t* h_lang_pos;        /* [n_windows] */
+  int32_t* h_lang;                  /* out [n_windows] */
+  float* h_lang_prob;               /* out [n_windows] */
+  float* h_probs;                   /* out [n_windows][n_langs] or NULL */
+} wm_language_auto;
+int wm_generate_multilingual(wm_engine* e, const wm_generate_args* a, const wm_language_auto* la /* or NULL */,
+                             const uint64_t* h_seeds /* [n_windows] or NULL */, void* stream);
+
 /* ctranslate2 Whisper.align(encoder_output, start_sequence, text_tokens, num_frames, median_filter_width)
  * [FW↑] for ONE window (faster-whisper find_alignment, word_timestamps=True): teacher-forced decoder pass over
  * h_sot + <|notimestamps|> + h_text + <|endoftext|> with the n_heads (layer, head) alignment heads'

@@ -36,6 +36,12 @@ alternated call by call inside the same process as the two --lockstep-fallback f
 max_line_width=W with transcribe's defaults for the line count and the cue length; one JSON line per arm with
 "max_line_width" 0 or W (the lines of profiles/worker_call_captions.jsonl).  Without the option the argument is not
 passed at all.
+
+--multilingual (with --sections): per-window language switching (transcribe's multilingual) off and on at every point,
+alternated call by call inside the same process: multilingual=False, then multilingual=True; one JSON line per arm with
+"multilingual" false or true.  After the last point the same clip is timed in throughput mode (VLOG_AMD_THROUGHPUT's
+route), off and on alternated the same way, one JSON line per arm with "mode": "throughput" (the lines of
+profiles/worker_call_multilingual.jsonl).  Without the option the argument is not passed at all.
 """
 import argparse
 import json
@@ -140,13 +146,16 @@ def sectioned(model, args, spec, tmp):
 
     model.engine.align_batch = timed_align
 
-    # the arms timed at every point: (lockstep_fallback, max_line_width), None = the argument is not passed
+    # the arms timed at every point: (lockstep_fallback, max_line_width, multilingual), None = the argument is not passed
     widths = [None] if args.max_line_width is None else [0, args.max_line_width]
-    flags = [(f, w) for f in fallback_flags(args) for w in widths]
+    mls = [False, True] if args.multilingual else [None]
+    flags = [(f, w, ml) for f in fallback_flags(args) for w in widths for ml in mls]
 
-    def call(n, arm=(None, None)):
-        flag, width = arm
+    def call(n, arm=(None, None, None)):
+        flag, width, ml = arm
         kw = dict(language=None, task="transcribe", beam_size=5, vad_filter=True)
+        if ml is not None:
+            kw["multilingual"] = ml
         if args.temperature is not None:
             kw["temperature"] = args.temperature
         if flag is not None:
@@ -162,12 +171,14 @@ def sectioned(model, args, spec, tmp):
         segs = [{"start": s.start, "end": s.end, "text": s.text} for s in segments]
         generate_webvtt(segs)
         dt = time.perf_counter() - t
-        print(f"sections={n} lockstep_fallback={flag} max_line_width={width}: {dt:.3f} s", file=sys.stderr,
-              flush=True)                                                  # progress
+        print(f"sections={n} lockstep_fallback={flag} max_line_width={width} multilingual={ml} "
+              f"throughput={model.throughput}: {dt:.3f} s", file=sys.stderr, flush=True)             # progress
         return dt, info, len(segs)
 
     call(0)                                                        # warm-up (allocations, kernels)
-    for n in counts:
+    points = [(n, False) for n in counts] + ([(0, True)] if args.multilingual else [])
+    for n, throughput in points:
+        model.throughput = throughput                              # (the last point of --multilingual: throughput mode)
         for flag in flags:
             call(n, flag)                                          # (the slots and rows of this point)
         # the arms alternate call by call, so drift of the box lands on both; counters are kept per flag
@@ -191,7 +202,8 @@ def sectioned(model, args, spec, tmp):
             a = accs[flag]
             bounds = getattr(info.transcription_options, "section_frames", None)
             med = float(np.median(walls[flag]))
-            line = {"model": args.model, "weights": spec, "sections": n if n > 0 else None,
+            line = {"model": args.model, "weights": spec, "mode": "throughput" if throughput else "sequential",
+                    "sections": n if n > 0 else None,
                     "sections_planned": len(bounds) if bounds else 1,
                     "sections_in_flight": args.sections_in_flight, "audio_s": audio_s,
                     "duration_after_vad": round(info.duration_after_vad, 2),
@@ -210,6 +222,9 @@ def sectioned(model, args, spec, tmp):
                 line["align"] = {"calls": al["calls"] // args.repeats, "windows": al["groups"] // args.repeats,
                                  "s": round(al["s"] / args.repeats, 3),
                                  "ms_per_window": round(1e3 * al["s"] / max(al["groups"], 1), 3)}
+            if flag[2] is not None:
+                line["multilingual"] = flag[2]
+                line["multilingual_in_force"] = bool(info.transcription_options.multilingual)
             print(json.dumps(line), flush=True)
 
 
@@ -274,7 +289,12 @@ def main():
     ap.add_argument("--max-line-width", type=int, default=None,
                     help="with --sections: time caption shaping off (max_line_width=0) and on (this width) at every "
                          "point, alternated call by call (module docstring); default: the argument is not passed")
+    ap.add_argument("--multilingual", action="store_true",
+                    help="with --sections: time multilingual off and on at every point and, last, in throughput mode on "
+                         "the same clip, alternated call by call (module docstring)")
     args = ap.parse_args()
+    if args.multilingual and not args.sections:
+        raise SystemExit("--multilingual goes with --sections")
     if args.max_line_width is not None and (not args.sections or args.max_line_width < 1):
         raise SystemExit("--max-line-width takes a width >= 1 and goes with --sections")
     spec = f"synthetic:{args.model}:0" + ("" if args.random_weights else ":margin")

@@ -25,6 +25,7 @@ SYMBOLS = (
     "wm_set_sequence_bias",
     "wm_generate_seeded",
     "wm_language_id",
+    "wm_generate_multilingual",
 )
 
 
@@ -56,6 +57,14 @@ class GenerateArgsC(C.Structure):
     ]
 
 
+class LanguageAutoC(C.Structure):
+    _fields_ = [
+        ("lang_begin", C.c_int32), ("n_langs", C.c_int32), ("h_allowed", C.POINTER(C.c_uint8)),
+        ("h_lang_pos", C.POINTER(C.c_int32)), ("h_lang", C.POINTER(C.c_int32)), ("h_lang_prob", C.POINTER(C.c_float)),
+        ("h_probs", C.POINTER(C.c_float)),
+    ]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -84,6 +93,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         "wm_cross_kv": (C.c_int, [vp, vp, i32, i32, vp]),
         "wm_generate": (C.c_int, [vp, C.POINTER(GenerateArgsC), vp]),
         "wm_generate_seeded": (C.c_int, [vp, C.POINTER(GenerateArgsC), C.POINTER(C.c_uint64), vp]),
+        "wm_generate_multilingual": (C.c_int, [vp, C.POINTER(GenerateArgsC), C.POINTER(LanguageAutoC),
+                                               C.POINTER(C.c_uint64), vp]),
         "wm_set_sequence_bias": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float), vp]),
         "wm_forward": (C.c_int, [vp, i32, C.POINTER(i32), i32, C.POINTER(i32), vp, i32, C.POINTER(i32), i32, vp, vp]),
         "wm_frame_energy": (C.c_int, [vp, vp, i64, i32, vp, vp]),

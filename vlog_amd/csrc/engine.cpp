@@ -137,6 +137,16 @@ static const int kDecPlanPresets[2][DEC_NPROJ] = {{0, -1, -1, -1, 0, -1}, {96, 3
 static const int kDecColsPresets[2][DEC_NPROJ] = {{32, 32, 32, 32, 32, 32}, {32, 32, 32, 32, 64, 64}};
 
 // Decoder weight pointers per layer (resolved once: the arena layout is fixed at wm_create).
+// wm_generate_multilingual: the running call's language state.  The auto windows (h_lang_pos >= 0) were identified
+// before generate() runs; their best indices stay on the device (d_top, by auto index) and lang_assign puts the tokens
+// into the call's prompt tables before the pass that prefills them.
+struct LangCall {
+  int lang_begin = 0, n_langs = 0;
+  std::vector<int> pos, aidx;     // [n_windows]: the language position (-1: the window keeps its prompt), the auto index
+  const int* d_top = nullptr;     // [auto windows]
+  std::vector<int> h_ent;         // host image of a row-set event's entry list (alive until the next poll synchronises)
+};
+
 struct DecLayerW {
   const bf16 *qkv_w, *out_w, *cq_w, *cout_w, *fc1_w, *fc2_w;
   const float *qkv_b, *out_b, *cq_b, *cout_b, *fc1_b, *fc2_b, *ln1_w, *ln1_b, *ln2_w, *ln2_b, *ln3_w, *ln3_b;
@@ -177,6 +187,14 @@ struct wm_engine {
   // per-window seeds (wm_generate_seeded; search.h hyp_seed / hyp_key): the running call's host seeds [n_windows]
   // (nullptr outside such a call) and the device tables
   const uint64_t* call_seeds = nullptr;
+  // wm_generate_multilingual: the running call's language state (nullptr outside such a call), its device tables
+  // ([4] error word | [n] top | [n] top probability | [n][n_langs] probabilities) and lang_assign's entry list
+  LangCall* call_lang = nullptr;
+  DevBuf d_la, d_la_ent;
+  // ... and the pinned host image of d_la: its copy back is queued behind the language head and has arrived when
+  // generate()'s own final synchronise returns (pinned, so the copy is asynchronous to the host)
+  void* h_la = nullptr;
+  size_t h_la_bytes = 0;
   DevBuf d_hyp_seed, d_hyp_key, d_win_seed;
   std::vector<int> h_ev;     // host image of d_ev (kept alive until the next poll syncs the stream)
   // sequence-bias table (wm_set_sequence_bias; search.h bias_*): allocated once at the limits' size, so a captured
@@ -1262,6 +1280,43 @@ void write_stats(const wm_generate_args* a, long long passes, long long row_step
   }
 }
 
+// wm_generate_multilingual: entries (offset into `table`, auto index), two ints each -> the chosen language tokens into
+// `table`, on `s`.  `ent` must stay alive until the stream has taken it.
+void lang_assign(wm_engine* e, const std::vector<int>& ent, int* table, hipStream_t s) {
+  const LangCall* lc = e->call_lang;
+  if (!lc || ent.empty()) return;
+  e->d_la_ent.ensure(ent.size() * 4);
+  HIP_OK(hipMemcpyAsync(e->d_la_ent.p, ent.data(), ent.size() * 4, hipMemcpyHostToDevice, s));
+  launch_lang_assign((int)ent.size() / 2, e->d_la_ent.as<int>(), lc->d_top, lc->lang_begin, lc->n_langs, table, s);
+}
+
+// ... the row-set forms' per-window prompt table (every window is identified before the call's first pass)
+void lang_assign_windows(wm_engine* e, int W, int P, hipStream_t s, std::vector<int>* ent) {
+  const LangCall* lc = e->call_lang;
+  if (!lc) return;
+  for (int w = 0; w < W; ++w)
+    if (lc->pos[w] >= 0) { ent->push_back(w * P + lc->pos[w]); ent->push_back(lc->aidx[w]); }
+  // (sized for any event's list, so no event moves it under a captured step graph: a start lists its language row,
+  // and the beam form's padding copies of it, at most 8 rows)
+  e->d_la_ent.ensure((size_t)W * 8 * 2 * 4);
+  lang_assign(e, *ent, e->d_win_prompt.as<int>(), s);
+}
+
+// ... the lockstep form: every hypothesis' token row, and the prefill rows (set i's rows start at pf_at[i])
+void lang_assign_lockstep(wm_engine* e, int NH, int per, int pf_per, int C, const std::vector<int>& pf_at, hipStream_t s,
+                          std::vector<int>* ent_tok, std::vector<int>* ent_row) {
+  const LangCall* lc = e->call_lang;
+  if (!lc) return;
+  for (int h = 0; h < NH; ++h) {
+    const int w = h / per;
+    if (lc->pos[w] < 0) continue;
+    ent_tok->push_back(h * C + lc->pos[w]); ent_tok->push_back(lc->aidx[w]);
+    if (h % pf_per == 0) { ent_row->push_back(pf_at[h / pf_per] + lc->pos[w]); ent_row->push_back(lc->aidx[w]); }
+  }
+  lang_assign(e, *ent_tok, e->d_tokens.as<int>(), s);
+  lang_assign(e, *ent_row, e->d_prow_tok.as<int>(), s);
+}
+
 // The lists of one row-set event pass, carved from one int array: the host image e->h_ev (zero-filled here; it lives on
 // the engine until the next poll synchronises the stream) and, at the same offsets, its device copy d_ev:
 // ptok, ppos, phyp, psrc [np] | row set [nr] | logit rows [nr + nsot] | start slots (groups), windows [nst] | live count
@@ -1489,6 +1544,9 @@ void generate(wm_engine* e, const wm_generate_args* a, hipStream_t st) {
     std::vector<int> ident(NH);
     for (int h = 0; h < NH; ++h) ident[h] = h;
     HIP_OK(hipMemcpyAsync(e->d_row_hyp.p, ident.data(), NH * 4, hipMemcpyHostToDevice, st));
+    // multilingual call: the chosen language tokens into every hypothesis' prompt and into the prefill rows
+    std::vector<int> ent_tok, ent_row;
+    lang_assign_lockstep(e, NH, per, pf_per, C, pf_at, st, &ent_tok, &ent_row);
     HIP_OK(hipStreamSynchronize(st));   // host vectors above go out of scope
   }
   float* logits = e->s_logits.as<float>();
@@ -1711,9 +1769,10 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
   HIP_OK(hipMemsetAsync(e->d_res_ns.p, 0, (size_t)W * 4, st));
   HIP_OK(hipMemsetAsync(e->d_n_active.p, 0, 4 * 4, st));      // live counter, error word
   {
-    std::vector<int> ones(R, 1);               // every slot starts ended (no hypothesis)
+    std::vector<int> ones(R, 1), ent;          // every slot starts ended (no hypothesis)
     HIP_OK(hipMemcpyAsync(e->d_done.p, ones.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
-    upload_suppress(e, a, st);                 // (synchronises: `ones` goes out of scope)
+    lang_assign_windows(e, W, P, st, &ent);
+    upload_suppress(e, a, st);                 // (synchronises: `ones` and `ent` go out of scope)
   }
   // pass rows: R decode rows + P prompt rows per starting window; logits rows: R + one sot row per start
   ensure_step(e, R * (1 + wa.Pmax), 2 * R);
@@ -1766,6 +1825,8 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
     const EventLists ev(e, np, nr, nsot, nst);
     const EventLists::Ptrs &u = ev.h, &d = ev.d;
     *u.n_live = n_live;
+    LangCall* lc = e->call_lang;                // multilingual call: the starting windows' language rows
+    if (lc) lc->h_ent.clear();
     int i = 0, k = 0;
     for (int r = 0; r < nr; ++r) {
       u.rh[r] = new_row_hyp[r];
@@ -1779,6 +1840,7 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
         for (int p = 0; p < Pw; ++p, ++i) {
           u.ptok[i] = a->h_prompts[(size_t)w * P + p]; u.ppos[i] = p; u.phyp[i] = h; u.psrc[i] = -1;
           if (p == sot) u.lr[nr + k] = i;
+          if (lc && p == lc->pos[w]) { lc->h_ent.push_back(i); lc->h_ent.push_back(lc->aidx[w]); }
         }
         u.lr[r] = i - 1;                        // the last prompt position predicts the first token
         u.hs[k] = h; u.ws[k] = w;
@@ -1788,6 +1850,7 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
       }
     }
     ev.upload(e, s);
+    if (lc) lang_assign(e, lc->h_ent, d.ptok, s);
     // carried rows read token / position from the last selection's (old) row order before it is overwritten
     launch_rows_fill(np, d.psrc, d.ptok, d.ppos, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
     launch_hyp_start(nst, d.hs, d.ws, e->d_win_prompt.as<int>(), P, e->d_win_slot.as<int>(), C, e->d_tokens.as<int>(),
@@ -1892,7 +1955,7 @@ void generate_rows(wm_engine* e, const wm_generate_args* a, const WinArgs& wa, h
 // then holds the last hidden state of sequence s at position p, on `st`, until the next pass
 void forward(wm_engine* e, int n_seq, const int* h_slots, int S, const int* h_tokens, float* d_logits, int last_only,
              const int* h_align, int n_align, float* d_attn, hipStream_t st, const std::vector<int>* logit_rows = nullptr,
-             bool hidden_only = false) {
+             bool hidden_only = false, std::vector<std::vector<int>>* keep = nullptr) {
   check_weights(e);
   const auto& m = e->dm;
   const int C = m.n_text_ctx, H = m.n_head;
@@ -1942,6 +2005,10 @@ void forward(wm_engine* e, int n_seq, const int* h_slots, int S, const int* h_to
   decoder_pass(e, rows, e->d_prow_tok.as<int>(), e->d_prow_pos.as<int>(), e->d_prow_hyp.as<int>(), nullptr,
                e->d_lin.as<int>(), e->d_logit_rows.as<int>(), nlog, hidden_only ? nullptr : d_logits,
                n_align ? &amap : nullptr, n_align, n_align ? d_attn : nullptr, S, st);
+  if (keep) {                                   // the caller keeps the uploads' host images alive and waits later
+    for (auto* v : {&rt, &rp, &rh, &lr, &hs, &lin}) keep->push_back(std::move(*v));
+    return;
+  }
   HIP_OK(hipStreamSynchronize(st));
 }
 
@@ -2002,9 +2069,10 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
   HIP_OK(hipMemsetAsync(e->d_res_ns.p, 0, (size_t)W * 4, st));
   HIP_OK(hipMemsetAsync(e->d_n_active.p, 0, 4 * 4, st));
   {
-    std::vector<int> ones(NH, 1);              // every group starts ended (no window)
+    std::vector<int> ones(NH, 1), ent;         // every group starts ended (no window)
     HIP_OK(hipMemcpyAsync(e->d_done.p, ones.data(), (size_t)NH * 4, hipMemcpyHostToDevice, st));
-    upload_suppress(e, a, st);                 // (synchronises: `ones` goes out of scope)
+    lang_assign_windows(e, W, P, st, &ent);
+    upload_suppress(e, a, st);                 // (synchronises: `ones` and `ent` go out of scope)
   }
   // pass rows: every hypothesis row + P prompt rows per starting group; logits rows: one per hypothesis row + one
   // sot row per start
@@ -2075,6 +2143,8 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
     const EventLists ev(e, np, nr, nsot, nst);
     const EventLists::Ptrs &u = ev.h, &d = ev.d;
     *u.n_live = n_live;
+    LangCall* lc = e->call_lang;                // multilingual call: the starting windows' language rows
+    if (lc) lc->h_ent.clear();
     int i = 0, r = 0;
     for (int g : nset) {
       const int h0 = g * K, k = start_of[g];
@@ -2085,10 +2155,12 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
         for (int p = 0; p < Pw; ++p, ++i) {
           u.ptok[i] = a->h_prompts[(size_t)w * P + p]; u.ppos[i] = p; u.phyp[i] = h0; u.psrc[i] = -1;
           if (p == sot) u.lr[nr + k] = i;
+          if (lc && p == lc->pos[w]) { lc->h_ent.push_back(i); lc->h_ent.push_back(lc->aidx[w]); }
           last = i;
         }
         for (int p = Pw; ev_group > 1 && p < PR; ++p, ++i) {   // (grouped rows: every window has Pw = Pmax <= K)
           u.ptok[i] = a->h_prompts[(size_t)w * P + Pw - 1]; u.ppos[i] = Pw - 1; u.phyp[i] = h0; u.psrc[i] = -1;
+          if (lc && Pw - 1 == lc->pos[w]) { lc->h_ent.push_back(i); lc->h_ent.push_back(lc->aidx[w]); }
         }
         for (int b = 0; b < K; ++b, ++r) { u.rh[r] = h0 + b; u.lr[r] = last; }
         u.hs[k] = g; u.ws[k] = w;
@@ -2100,6 +2172,7 @@ void generate_rows_beam(wm_engine* e, const wm_generate_args* a, const WinArgs& 
       }
     }
     ev.upload(e, s);
+    if (lc) lang_assign(e, lc->h_ent, d.ptok, s);
     // carried rows: token / position of their hypothesis from the last beam selection (hypothesis-indexed)
     launch_rows_fill(np, d.psrc, d.ptok, d.ppos, e->d_row_tok.as<int>(), e->d_row_pos.as<int>(), s);
     launch_beam_start(nst, d.hs, d.ws, K, e->d_win_prompt.as<int>(), P, e->d_win_slot.as<int>(), C, e->d_tokens.as<int>(),
@@ -2659,9 +2732,11 @@ void wm_destroy(wm_engine* e) {
                     &e->a_pj, &e->a_plen, &e->a_meta, &e->a_enc, &e->a_kv, &e->d_tok_lp, &e->d_tok_lp_o, &e->d_fin_lp, &e->d_win_prompt,
                     &e->d_win_slot, &e->d_hyp_out, &e->d_res_tok, &e->d_res_len, &e->d_res_cum, &e->d_res_ns, &e->d_res_lp,
                     &e->d_res_lp_o, &e->d_ev, &e->d_hyp_begin, &e->d_hyp_maxlen, &e->d_win_len, &e->d_win_maxlen,
-                    &e->d_sb_off, &e->d_sb_tok, &e->d_sb_val, &e->d_hyp_seed, &e->d_hyp_key, &e->d_win_seed})
+                    &e->d_sb_off, &e->d_sb_tok, &e->d_sb_val, &e->d_hyp_seed, &e->d_hyp_key, &e->d_win_seed,
+                    &e->d_la, &e->d_la_ent})
     b->release();
   for (auto& kv : e->rs_taps) kv.second.pp.release();
+  if (e->h_la) (void)hipHostFree(e->h_la);
   if (e->st2) (void)hipStreamDestroy(e->st2);
   if (e->gst) (void)hipStreamDestroy(e->gst);
   if (e->ev_g0) (void)hipEventDestroy(e->ev_g0);
@@ -2826,6 +2901,120 @@ int wm_generate_seeded(wm_engine* e, const wm_generate_args* a, const uint64_t* 
       ~SeedScope() { e->call_seeds = nullptr; }
     } scope(e, a->temperature > 0.f ? h_seeds : nullptr);
     generate(e, a, (hipStream_t)stream);
+  });
+}
+
+int wm_generate_multilingual(wm_engine* e, const wm_generate_args* a, const wm_language_auto* la, const uint64_t* h_seeds,
+                             void* stream) {
+  if (!la) return wm_generate_seeded(e, a, h_seeds, stream);
+  return guarded(e, [&] {
+    require_weights(e);
+    const std::string who = "wm_generate_multilingual: ";
+    const int n_langs = la->n_langs, lang_begin = la->lang_begin;
+    if (n_langs <= 0 || n_langs > SEARCH_LANG_MAX)
+      throw std::runtime_error(who + "n_langs outside 1.." + std::to_string(SEARCH_LANG_MAX));
+    if (lang_begin < 0 || lang_begin + n_langs > e->dm.n_vocab)
+      throw std::runtime_error(who + "lang_begin .. lang_begin + n_langs outside the vocabulary");
+    if (la->h_allowed && std::none_of(la->h_allowed, la->h_allowed + n_langs, [](uint8_t v) { return v != 0; }))
+      throw std::runtime_error(who + "h_allowed sets no language");
+    const int W = a->n_windows;
+    if (W <= 0) return;
+    if (!la->h_lang_pos || !la->h_lang || !la->h_lang_prob) throw std::runtime_error(who + "null argument");
+    const WinArgs wa = window_args(e, a);
+    LangCall lc;
+    lc.lang_begin = lang_begin; lc.n_langs = n_langs;
+    lc.pos.assign(W, -1); lc.aidx.assign(W, -1);
+    std::vector<int> slots;                                  // the auto windows' slots, in call order
+    for (int w = 0; w < W; ++w) {
+      const int pos = la->h_lang_pos[w];
+      if (pos < 0) continue;
+      const std::string ww = who + "window " + std::to_string(w) + ": ";
+      if (pos >= wa.len[w])
+        throw std::runtime_error(ww + "language position " + std::to_string(pos) + " outside its prompt of " +
+                                 std::to_string(wa.len[w]) + " tokens");
+      const int* pr = a->h_prompts + (size_t)w * a->prompt_len;
+      if (pr[pos] < lang_begin || pr[pos] >= lang_begin + n_langs)
+        throw std::runtime_error(ww + "token " + std::to_string(pr[pos]) + " at language position " + std::to_string(pos) +
+                                 " is not a language token");
+      if (pos == 0 || pr[pos - 1] != e->dm.sot)
+        throw std::runtime_error(ww + "the token before language position " + std::to_string(pos) +
+                                 " is not <|startoftranscript|>");
+      if (a->h_slots[w] < 0 || a->h_slots[w] >= e->n_slots) throw std::runtime_error(ww + "slot outside the reserved slots");
+      lc.pos[w] = pos; lc.aidx[w] = (int)slots.size();
+      slots.push_back(a->h_slots[w]);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int n = (int)slots.size(), d = e->dm.n_state;
+    std::vector<std::vector<int>> keep;                      // the detection passes' uploads (no wait of their own)
+    int* err = nullptr;
+    float* d_probs = nullptr;
+    if (n > 0) {
+      // wm_language_id over the auto windows: the same passes (160 rows each, in call order), the same head, but the
+      // results stay on the device and nothing waits for them.  Hypothesis capacity for a pass is reserved here, once:
+      // generate()'s own reserve then grows the tables or leaves them, before it takes any pointer into them, and the
+      // self-KV the passes write (position 0 of their rows) is overwritten by the prefill before anything reads it.
+      constexpr int PASS = 160;
+      reserve(e, e->n_slots, std::min(n, PASS));
+      e->d_la.ensure((4 + (size_t)n * (2 + n_langs)) * 4);
+      e->a_meta.ensure((size_t)SEARCH_LANG_MAX);
+      err = e->d_la.as<int>() + 1;                           // (an error word of its own: generate() clears the decode's)
+      int* d_top = e->d_la.as<int>() + 4;
+      float* d_top_prob = (float*)(d_top + n);
+      d_probs = d_top_prob + n;
+      HIP_OK(hipMemsetAsync(e->d_la.p, 0, 4 * 4, st));
+      if (la->h_allowed) HIP_OK(hipMemcpyAsync(e->a_meta.p, la->h_allowed, n_langs, hipMemcpyHostToDevice, st));
+      const std::vector<int> toks(std::min(n, PASS), e->dm.sot);
+      for (int r0 = 0; r0 < n; r0 += PASS) {
+        const int nr = std::min(PASS, n - r0);
+        forward(e, nr, slots.data() + r0, 1, toks.data(), nullptr, 1, nullptr, 0, nullptr, st, nullptr, true, &keep);
+        launch_lang_head(e->s_x.as<float>(), d, nr, d, e->Wf("dec.ln.w"), e->Wf("dec.ln.b"), e->Wb("dec.embed"), lang_begin,
+                         n_langs, la->h_allowed ? e->a_meta.as<unsigned char>() : nullptr, d_probs + (size_t)r0 * n_langs,
+                         d_top + r0, d_top_prob + r0, r0, err, st);
+      }
+      lc.d_top = d_top;
+      // the results' way back: queued here, delivered by generate()'s own final synchronise (no wait of its own)
+      const size_t nb = (4 + (size_t)n * (2 + n_langs)) * 4;
+      if (nb > e->h_la_bytes) {
+        if (e->h_la) HIP_OK(hipHostFree(e->h_la));
+        e->h_la = nullptr;
+        e->h_la_bytes = 0;
+        HIP_OK(hipHostMalloc(&e->h_la, nb, hipHostMallocDefault));
+        e->h_la_bytes = nb;
+      }
+      HIP_OK(hipMemcpyAsync(e->h_la, e->d_la.p, nb, hipMemcpyDeviceToHost, st));
+    }
+    struct Scope {                        // the seeds and the language state belong to this call alone
+      wm_engine* e;
+      Scope(wm_engine* e_, const uint64_t* s, LangCall* l) : e(e_) { e->call_seeds = s; e->call_lang = l; }
+      ~Scope() { e->call_seeds = nullptr; e->call_lang = nullptr; }
+    } scope(e, a->temperature > 0.f ? h_seeds : nullptr, n > 0 ? &lc : nullptr);
+    try {
+      generate(e, a, st);
+    } catch (...) {
+      (void)hipStreamSynchronize(st);     // (`keep` and `slots` outlive whatever the stream still holds)
+      throw;
+    }
+    // generate() has synchronised the stream for its own results: the language results' copy, queued before it, is in
+    std::vector<float> host((size_t)n * (2 + n_langs) + 4, 0.f);
+    if (n > 0) std::memcpy(host.data(), e->h_la, host.size() * 4);
+    const int* h_top = (const int*)host.data() + 4;
+    const float* h_top_prob = host.data() + 4 + n;
+    const float* h_pr = h_top_prob + n;
+    int failed = -1;
+    for (int w = 0; w < W; ++w) {
+      const int i = lc.aidx[w];
+      la->h_lang[w] = i >= 0 ? h_top[i] : -1;
+      la->h_lang_prob[w] = i >= 0 ? h_top_prob[i] : 0.f;
+      if (la->h_probs) {
+        float* dst = la->h_probs + (size_t)w * n_langs;
+        if (i >= 0) std::memcpy(dst, h_pr + (size_t)i * n_langs, (size_t)n_langs * 4);
+        else std::fill(dst, dst + n_langs, 0.f);
+      }
+      if (i >= 0 && h_top[i] < 0 && failed < 0) failed = w;
+    }
+    if (failed >= 0)
+      throw std::runtime_error(who + "non-finite language logits, window " + std::to_string(failed) +
+                               " (row " + std::to_string(((const int*)host.data())[2]) + ")");
   });
 }
 

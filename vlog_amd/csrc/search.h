@@ -127,6 +127,10 @@ void launch_lang_probs(const float* logits, long long ldl, int rows, int lang_be
 void launch_lang_head(const float* x, long long ldx, int rows, int d, const float* g, const float* b, const bf16* E,
                       int lang_begin, int n_langs, const unsigned char* allowed, float* probs, int* top_id,
                       float* top_prob, int row0, int* err, hipStream_t st);
+// Language assignment (wm_generate_multilingual): table[ent[2i]] = lang_begin + top[ent[2i + 1]] for i < n, where top is
+// launch_lang_head's top_id table on the device (an entry whose top is outside [0, n_langs) is skipped).  The caller has
+// checked every offset against its table.
+void launch_lang_assign(int n, const int* ent, const int* top, int lang_begin, int n_langs, int* table, hipStream_t st);
 // out[out_idx ? out_idx[r] : r] = softmax(logits row r)[no_speech]
 void launch_no_speech(const float* logits, long long ldl, int V, int rows, int no_speech, float* out, hipStream_t st,
                       const int* out_idx = nullptr);

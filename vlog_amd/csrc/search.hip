@@ -1098,6 +1098,22 @@ void launch_lang_head(const float* x, long long ldx, int rows, int d, const floa
   WM_LAUNCH_CHECK("lang_head_kernel");
 }
 
+// wm_generate_multilingual: entry i = (ent[2i], ent[2i + 1]) puts the language token chosen for auto window ent[2i + 1]
+// into table[ent[2i]].  A window whose head failed (top < 0; the call then fails at its end) keeps its placeholder.
+__global__ __launch_bounds__(256) void lang_assign_kernel(int n, const int* __restrict__ ent, const int* __restrict__ top,
+                                                          int lang_begin, int n_langs, int* __restrict__ table) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int t = top[ent[2 * i + 1]];
+  if (t >= 0 && t < n_langs) table[ent[2 * i]] = lang_begin + t;
+}
+
+void launch_lang_assign(int n, const int* ent, const int* top, int lang_begin, int n_langs, int* table, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(lang_assign_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, ent, top, lang_begin, n_langs, table);
+  WM_LAUNCH_CHECK("lang_assign_kernel");
+}
+
 // softmax(logits[r])[no_speech]
 __global__ __launch_bounds__(SB) void no_speech_kernel(const float* __restrict__ logits, long long ldl, int V, int ns,
                                                         float* __restrict__ out, const int* __restrict__ out_idx) {

@@ -363,7 +363,8 @@ class GpuEngine:
                  repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  prompt_lens: Optional[Sequence[int]] = None,
                  sequence_bias: Optional[Sequence[Tuple[Sequence[int], float]]] = None,
-                 seeds: Optional[Sequence[int]] = None) -> Tuple[List[GenResult], int]:
+                 seeds: Optional[Sequence[int]] = None,
+                 language_auto: Optional[dict] = None) -> Tuple[List[GenResult], int]:
         """ctranslate2 Whisper.generate over windows in slots (wm_generate).  max_rows / compact: the row-set decode
         (greedy / one sampled hypothesis; windows refill finished rows in the given order, include/whisper_mi355.h);
         beam search with compact drops finished windows' hypotheses from the passes.
@@ -383,7 +384,12 @@ class GpuEngine:
         one-length arguments (NULL for the three per-window pointers).
         seeds: one sampling seed per window (wm_generate_seeded; each taken mod 2^64 like `seed`, which is then not
         read): window w's hypothesis j draws its noise from (seeds[w], j), so the window's result is that of a call
-        with it alone and seed=seeds[w], wherever it stands in the call.  None calls wm_generate."""
+        with it alone and seed=seeds[w], wherever it stands in the call.  None calls wm_generate.
+        language_auto: dict(lang_begin, n_langs, allowed, positions) (wm_generate_multilingual): window w with
+        positions[w] >= 0 is identified on the device before its prefill and the chosen language token replaces the
+        placeholder at that prompt position (-1: the window keeps its prompt; `allowed` as language_id's, None = all).
+        The call then returns (results, steps, (top [W] i32, top_prob [W] f32, probs [W, n_langs] f32)), top -1 where
+        the position is -1."""
         W = len(slots)
         h_seeds = None
         if seeds is not None:
@@ -449,11 +455,32 @@ class GpuEngine:
             _f32p(lpo) if lpo is not None else None, st64.ctypes.data_as(C.POINTER(C.c_int64)),
             float(repetition_penalty), int(no_repeat_ngram_size),
             _i32p(h_lens) if ragged else None, _i32p(h_sots) if ragged else None, _i32p(h_mls) if ragged else None)
+        la = lang_out = None
+        if language_auto is not None:
+            n_langs = int(language_auto["n_langs"])
+            h_pos = np.ascontiguousarray(language_auto["positions"], dtype=np.int32)
+            if h_pos.shape != (W,):
+                raise ValueError("language_auto: positions needs one entry per window")
+            mask = None
+            if language_auto.get("allowed") is not None:
+                mask = np.ascontiguousarray(np.asarray(language_auto["allowed"]) != 0, dtype=np.uint8)
+                if mask.shape != (n_langs,):
+                    raise ValueError(f"language_auto: allowed must have n_langs = {n_langs} entries, got {mask.shape}")
+            lang_out = (np.full(W, -1, dtype=np.int32), np.zeros(W, dtype=np.float32),
+                        np.zeros((W, max(n_langs, 0)), dtype=np.float32))
+            la = _capi.LanguageAutoC(int(language_auto["lang_begin"]), n_langs,
+                                     mask.ctypes.data_as(C.POINTER(C.c_uint8)) if mask is not None else None,
+                                     _i32p(h_pos), _i32p(lang_out[0]), _f32p(lang_out[1]), _f32p(lang_out[2]))
         with torch.cuda.device(self.device):
             if sequence_bias:
                 self.set_sequence_bias(sequence_bias)
             try:
-                if h_seeds is None:
+                if la is not None:
+                    _capi.check(self.lib.wm_generate_multilingual(
+                        self.h, C.byref(a), C.byref(la),
+                        h_seeds.ctypes.data_as(C.POINTER(C.c_uint64)) if h_seeds is not None else None,
+                        self.stream_ptr()), "wm_generate_multilingual")
+                elif h_seeds is None:
                     _capi.check(self.lib.wm_generate(self.h, C.byref(a), self.stream_ptr()), "wm_generate")
                 else:
                     _capi.check(self.lib.wm_generate_seeded(self.h, C.byref(a), h_seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
@@ -472,6 +499,8 @@ class GpuEngine:
             res.append(r)
         if stats is not None:
             stats.update(passes=int(st64[0]), row_steps=int(st64[1]), refills=int(st64[2]), graph_captures=int(st64[3]))
+        if lang_out is not None:
+            return res, int(steps[0]), lang_out
         return res, int(steps[0])
 
     def set_sequence_bias(self, table: Sequence[Tuple[Sequence[int], float]]) -> None:

@@ -35,6 +35,10 @@ class WindowRequest:
     duration: float
     prompt: List[int]
     max_length: int        # total decoder length of this window, prompt included
+    # multilingual=True: the language code the prompt carries (a placeholder until the window's first decode has
+    # detected its language: SeekState.set_window_language) and that token's position in the prompt; else None / -1
+    language: Optional[str] = None
+    lang_pos: int = -1
 
 
 def window_max_length(prompt: Sequence[int], max_new_tokens: Optional[int], model_max_length: int) -> int:
@@ -167,6 +171,12 @@ class SeekState:
         self.last_speech_timestamp = 0.0
         self.window = 0
         self._request: Optional[WindowRequest] = None
+        # multilingual=True (faster-whisper's code switching): every window is decoded under the language detected for
+        # it.  `language` is the code the next window's prompt starts from: the file's, then the previous window's.
+        # An English-only tokenizer has no language token: the option is off.
+        self.multilingual = bool(getattr(options, "multilingual", False)) and \
+            getattr(tokenizer, "language", None) is not None
+        self.language: Optional[str] = tokenizer.language_code if self.multilingual else None
 
     def next_request(self) -> Optional[WindowRequest]:
         """The window to decode next (the same object until it is consumed), or None when the file is done."""
@@ -185,6 +195,8 @@ class SeekState:
                 continue
             seek = self.seek
             size = min(N_FRAMES, self.content_frames - seek, clip_end - seek)
+            if self.multilingual:
+                tk = tk.for_language(self.language)
             prompt = segs.build_prompt(tk.encode, tk.sot_sequence, tk.sot_prev, tk.no_timestamps, tk.timestamp_begin,
                                        self.model_max_length, self.all_tokens[self.prompt_reset_since:],
                                        o.without_timestamps, prefix=o.prefix if seek == 0 else None, hotwords=o.hotwords)
@@ -192,15 +204,49 @@ class SeekState:
                                           time_offset=seek * HOP_LENGTH / SAMPLE_RATE,
                                           duration=size * HOP_LENGTH / SAMPLE_RATE, prompt=prompt,
                                           max_length=window_max_length(prompt, o.max_new_tokens, self.model_max_length))
+            if self.multilingual:
+                self._request.language = self.language
+                self._request.lang_pos = prompt.index(tk.sot) + 1
             return self._request
         return None
+
+    def set_window_language(self, code: Optional[str]) -> None:
+        """multilingual=True: the language the pending window's first decode detected (the `language` of its result;
+        faster-whisper detects once per window, before the fallback loop).  The request's prompt then carries that
+        language's token, so every fallback temperature decodes under it, and consume() aligns and labels the window
+        with it and hands it to the next window as its placeholder.  A no-op with the option off or code None."""
+        req = self._request
+        if req is None:
+            raise RuntimeError("SeekState.set_window_language without a pending request")
+        if not self.multilingual or code is None:
+            return
+        req.prompt[req.lang_pos] = self.tokenizer.for_language(code).language
+        req.language = code
 
     def consume(self, decode_result: Tuple[object, float, float, float],
                 align: Optional[Callable[[List[dict], int, float], float]] = None) -> List[dict]:
         """Takes the pending window's (result, avg_logprob, temperature, compression_ratio) and returns the segments
         to yield, as dicts with the fields of `Segment` (words: the aligned word dicts or None).
         align(current_segments, segment_size, last_speech_timestamp) -> last_speech_timestamp adds the word times in
-        place (word_timestamps; it runs before the seek position is final, which depends on the last word's end)."""
+        place (word_timestamps; it runs before the seek position is final, which depends on the last word's end).
+        multilingual=True: the window's language is its request's (set_window_language); align is then called with
+        tokenizer=<that language's tokenizer> (its sot_sequence and word splitting), every segment dict carries
+        language=<code>, and the next window's prompt starts from it.
+        The two halves, for a driver that aligns several states' windows in one call: begin_consume, finish_consume."""
+        item = self.begin_consume(decode_result)
+        if item is None:
+            return self.finish_consume()
+        current, size, last, tk = item
+        if self.multilingual:
+            return self.finish_consume(align(current, size, last, tokenizer=tk))
+        return self.finish_consume(align(current, size, last))
+
+    def begin_consume(self, decode_result: Tuple[object, float, float, float]):
+        """The first half of consume: everything before the word alignment.  -> None when nothing is to be aligned (the
+        window is skipped as silence, or word_timestamps is off), else (current_segments, segment_size,
+        last_speech_timestamp, tokenizer): the caller adds the word times to current_segments in place, under that
+        tokenizer (the window's language's with multilingual=True), and passes the new last-speech time to
+        finish_consume."""
         req = self._request
         if req is None:
             raise RuntimeError("SeekState.consume without a pending request")
@@ -208,14 +254,31 @@ class SeekState:
         o, tk = self.options, self.tokenizer
         result, avg_lp, temperature, cr = decode_result
         self.window += 1
+        if self.multilingual:
+            self.language = req.language
         if segs.should_skip_window(result.no_speech_prob, avg_lp, o.no_speech_threshold, o.log_prob_threshold):
             self.seek += req.size
-            return []
-        previous_seek = req.seek
+            self._begun = (req, decode_result, None, True)
+            return None
         current, self.seek, single_ending = segs.split_segments_by_timestamps(
             result.tokens, tk.timestamp_begin, req.time_offset, req.size, req.duration, req.seek)
+        self._begun = (req, decode_result, current, single_ending)
+        if not o.word_timestamps:
+            return None
+        return current, req.size, self.last_speech_timestamp, tk.for_language(req.language) if self.multilingual else tk
+
+    def finish_consume(self, last_speech_timestamp: Optional[float] = None) -> List[dict]:
+        """The second half of consume: last_speech_timestamp is the alignment's (None when begin_consume returned
+        None).  -> the segments to yield."""
+        begun, self._begun = getattr(self, "_begun", None), None
+        if begun is None:
+            raise RuntimeError("SeekState.finish_consume without begin_consume")
+        req, (result, avg_lp, temperature, cr), current, single_ending = begun
+        if current is None:
+            return []
+        o, tk = self.options, self.tokenizer
         if o.word_timestamps:
-            self.last_speech_timestamp = align(current, req.size, self.last_speech_timestamp)
+            self.last_speech_timestamp = last_speech_timestamp
             if not single_ending:
                 last_word_end = _get_end(current)
                 if last_word_end is not None and last_word_end > req.time_offset:
@@ -227,12 +290,46 @@ class SeekState:
                 continue
             self.all_tokens.extend(s["tokens"])
             self.idx += 1
-            out.append(dict(id=self.idx, seek=previous_seek, start=s["start"], end=s["end"], text=text, tokens=s["tokens"],
+            out.append(dict(id=self.idx, seek=req.seek, start=s["start"], end=s["end"], text=text, tokens=s["tokens"],
                             temperature=temperature, avg_logprob=avg_lp, compression_ratio=cr,
                             no_speech_prob=result.no_speech_prob, words=s["words"] if o.word_timestamps else None))
+            if self.multilingual:
+                out[-1]["language"] = req.language
         if not o.condition_on_previous_text or temperature > o.prompt_reset_on_temperature:
             self.prompt_reset_since = len(self.all_tokens)
         return out
+
+
+def consume_round_grouped(batch, decodes, align_group, emit) -> None:
+    """The consume step of a lockstep round whose word alignment is grouped by language: every entry's window is split
+    (begin_consume), the entries with something to align are grouped by their tokenizer's sot sequence (with
+    multilingual=True the window's language's), align_group(items) is called ONCE per distinct sot sequence with
+    items = [(entry index, current_segments, segment_size, last_speech_timestamp, tokenizer)] in batch order and returns
+    one new last-speech time per item (each item keeps its own: the entries are different files or sections), and every
+    entry is finished and emitted in batch order."""
+    items = []
+    for i, (_, state, _) in enumerate(batch):
+        item = state.begin_consume(decodes[i])
+        if item is not None:
+            items.append((i,) + tuple(item))
+    groups: dict = {}
+    for it in items:
+        groups.setdefault(tuple(it[4].sot_sequence), []).append(it)
+    lasts: dict = {}
+    for group in groups.values():
+        out = align_group(group)
+        if len(out) != len(group):
+            raise RuntimeError("consume_round_grouped: align_group must return one last-speech time per item")
+        for it, last in zip(group, out):
+            lasts[it[0]] = last
+    for i, (f, state, _) in enumerate(batch):
+        emit(f, state.finish_consume(lasts.get(i)))
+
+
+def _grouped(batch, align, align_group) -> bool:
+    """a round aligns by language groups when the driver can (align_group) and some entry has multilingual on; every
+    other round keeps its one alignment call per entry, as before"""
+    return align is not None and align_group is not None and any(state.multilingual for _, state, _ in batch)
 
 
 def run_lockstep(n_files: int, max_files: int, open_file: Callable[[int], SeekState],
@@ -290,25 +387,38 @@ def decode_round_with(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
                       first_pass: Callable[[List[int]], List[object]],
                       fallback_generate: Callable[[int, float, int], object],
                       align: Optional[Callable[[int, List[dict], int, float], float]],
-                      emit: Callable[[int, List[dict]], None]) -> None:
+                      emit: Callable[[int, List[dict]], None], align_group=None) -> None:
     """One lockstep round over `batch` (entry i = cross slot i).
     first_pass(indices) -> the results at temperatures[0] of those entries, decoded together (the caller may split
-    them further, e.g. by suppress list); fallback_generate(i, temperature, seed) re-decodes entry i alone, for the
+    them further, e.g. by suppress list); with multilingual=True each result's `language` is the code detected for its
+    window, which the entry's request takes before any fallback (SeekState.set_window_language), and align receives
+    tokenizer=<that language's>; fallback_generate(i, temperature, seed) re-decodes entry i alone, for the
     temperatures after the first; align(i, segments, size, last_speech) word-aligns entry i against its own slot;
-    emit(file, segments) receives each file's new segments."""
+    emit(file, segments) receives each file's new segments.
+    align_group (consume_round_grouped): with it, a round in which some entry has multilingual on aligns its entries
+    in ONE call per distinct language among them instead of one call per entry; the ladders all run first."""
     firsts = first_pass(list(range(len(batch))))
+    if _grouped(batch, align, align_group):
+        decodes = []
+        for i, (f, state, req) in enumerate(batch):
+            state.set_window_language(getattr(firsts[i], "language", None))
+            decodes.append(fallback_ladder(lambda t, seed, i=i: fallback_generate(i, t, seed), state.tokenizer.decode,
+                                           state.options, seed=req.window, first=firsts[i]))
+        consume_round_grouped(batch, decodes, align_group, emit)
+        return
     for i, (f, state, req) in enumerate(batch):
+        state.set_window_language(getattr(firsts[i], "language", None))
         decode = fallback_ladder(lambda t, seed, i=i: fallback_generate(i, t, seed), state.tokenizer.decode, state.options,
                                  seed=req.window, first=firsts[i])
-        emit(f, state.consume(decode, (lambda cur, size, last, i=i: align(i, cur, size, last)) if align else None))
+        emit(f, state.consume(decode, (lambda cur, size, last, i=i, **kw: align(i, cur, size, last, **kw)) if align else None))
 
 
 def decode_round_levels(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
                         first_pass: Callable[[List[int]], List[object]],
                         level_pass: Callable[[List[int], float, List[int]], List[object]],
                         align: Optional[Callable[[int, List[dict], int, float], float]],
-                        emit: Callable[[int, List[dict]], None]) -> None:
-    """decode_round_with with the fallback ladder walked by LEVELS: the entries whose result at temperature i - 1
+                        emit: Callable[[int, List[dict]], None], align_group=None) -> None:
+    """decode_round_with (align_group included) with the fallback ladder walked by LEVELS: the entries whose result at temperature i - 1
     needs a fallback are re-decoded together.
     first_pass(indices): as decode_round_with.  level_pass(indices, temperature, seeds) -> the results of those
     entries at `temperature`, entry k with seeds[k]; level i is called once, with the entries still failing in batch
@@ -317,6 +427,8 @@ def decode_round_levels(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
     emitted in batch order, word-aligned (align, at consume time) against its own slot.  Per entry the decode tuple
     is what fallback_ladder returns for the same results."""
     firsts = first_pass(list(range(len(batch))))
+    for i, (_, state, _) in enumerate(batch):
+        state.set_window_language(getattr(firsts[i], "language", None))
     ladders = [FallbackLadder(state.tokenizer.decode, state.options, seed=req.window) for _, state, req in batch]
     failing = [i for i, ladder in enumerate(ladders) if not ladder.done and ladder.judge(firsts[i]) == NEXT]
     while failing:
@@ -328,9 +440,12 @@ def decode_round_levels(batch: Sequence[Tuple[int, SeekState, WindowRequest]],
         if len(results) != len(failing):
             raise RuntimeError("decode_round_levels: level_pass must return one result per entry")
         failing = [i for i, r in zip(failing, results) if ladders[i].judge(r) == NEXT]
+    if _grouped(batch, align, align_group):
+        consume_round_grouped(batch, [ladder.result() for ladder in ladders], align_group, emit)
+        return
     for i, (f, state, req) in enumerate(batch):
         emit(f, state.consume(ladders[i].result(),
-                              (lambda cur, size, last, i=i: align(i, cur, size, last)) if align else None))
+                              (lambda cur, size, last, i=i, **kw: align(i, cur, size, last, **kw)) if align else None))
 
 
 # ---------------------------------------------------------------------------------------------------- sections

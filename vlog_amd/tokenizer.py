@@ -13,6 +13,7 @@ Two vocabularies:
 """
 from __future__ import annotations
 
+import copy
 import os
 import string
 from functools import cached_property
@@ -173,6 +174,20 @@ class Tokenizer:
         if self.task is not None and self.multilingual:
             seq.append(self.task)
         return seq
+
+    def for_language(self, code: str) -> "Tokenizer":
+        """This tokenizer with another language (multilingual=True: a window decoded under the language detected for
+        it): the same vocabulary and task, `code`'s token in sot_sequence and its word-splitting rule.  Memoised per
+        code; an English-only tokenizer has no language token and returns itself."""
+        if self.language is None or code == self.language_code:
+            return self
+        memo = self.__dict__.setdefault("_by_language", {})
+        tk = memo.get(code)
+        if tk is None:
+            tk = memo[code] = copy.copy(self)
+            tk.__dict__.pop("_by_language", None)
+            tk.language_code, tk.language = code, self.st.lang_token(code)
+        return tk
 
     def encode(self, text: str) -> List[int]:
         return self.vocab.encode(text)

@@ -77,9 +77,13 @@ class Segment:
     no_speech_prob: float
     words: Optional[List[Word]]
     temperature: Optional[float]
+    language: Optional[str] = None      # multilingual=True: the language this segment's window was decoded under
 
     def _asdict(self):
-        return asdict(self)
+        d = asdict(self)
+        if self.language is None:           # with the option off a segment's dict is what it was
+            del d["language"]
+        return d
 
 
 @dataclass
@@ -159,6 +163,18 @@ class _GenOut:
     tokens: List[int]
     score: float
     no_speech_prob: float
+    language: Optional[str] = None      # multilingual=True, a window's first decode: the language detected for it
+
+
+def _resolve_multilingual(value: Optional[bool]) -> bool:
+    """The multilingual argument of the transcribe calls: None reads VLOG_AMD_MULTILINGUAL (0 / 1; unset or empty:
+    off)."""
+    if value is not None:
+        return bool(value)
+    env = os.environ.get("VLOG_AMD_MULTILINGUAL", "")
+    if env not in ("", "0", "1"):
+        raise ValueError(f"VLOG_AMD_MULTILINGUAL must be 0 or 1, got {env!r}")
+    return env == "1"
 
 
 def _resolve_lockstep_fallback(value: Optional[bool]) -> bool:
@@ -296,6 +312,38 @@ class WhisperModel:
         English-only model."""
         codes = self.dims.specials.lang_codes if self.is_multilingual else ()
         return candidates_in_force(value, os.environ, codes, self.is_multilingual, language)
+
+    def _multilingual(self, value: Optional[bool], languages: Sequence[Optional[str]] = ()) -> bool:
+        """The `multilingual` argument of a call -> what is in force: None reads VLOG_AMD_MULTILINGUAL; an English-only
+        model turns it off (logged once, as faster-whisper does).  languages: the languages the call names (None: to be
+        detected).  A call that names a language asks for that language in every window, so multilingual=True with it
+        stays refused with NotImplementedError, as it was; the environment's default is then simply off (logged once),
+        so a worker that configures a language keeps it."""
+        on = _resolve_multilingual(value)
+        if on and not self.is_multilingual:
+            if not getattr(self, "_warned_multilingual", False):
+                logger.warning("The current model is English-only but the multilingual parameter is set to True; "
+                               "setting to False instead.")
+                self._warned_multilingual = True
+            return False
+        named = [c for c in languages if c is not None]
+        if on and named:
+            if value is not None:
+                raise NotImplementedError(f"multilingual=True with language={named[0]!r} is not supported by the MI355X "
+                                          "engine: a named language holds for every window (pass language=None)")
+            if not getattr(self, "_warned_multilingual_named", False):
+                logger.warning("VLOG_AMD_MULTILINGUAL is ignored by calls that name their language")
+                self._warned_multilingual_named = True
+            return False
+        return on
+
+    def _language_auto(self, options, positions: Sequence[int]) -> dict:
+        """engine.generate's language_auto for a multilingual first decode: the language tokens, the call's whitelist as
+        the mask (language_candidates applies to the per-window detection too) and the windows' prompt positions."""
+        st = self.dims.specials
+        cand = options.language_candidates
+        return dict(lang_begin=st.lang_begin, n_langs=st.n_langs,
+                    allowed=candidate_mask(cand, st.lang_codes) if cand else None, positions=list(positions))
 
     def _sequence_bias(self, tokenizer: Tokenizer, sequence_bias):
         """The `sequence_bias` argument of a transcribe call -> (the mapping in force, the engine's table or None).
@@ -455,7 +503,7 @@ class WhisperModel:
                    prefix: Optional[str] = None, suppress_blank: bool = True, suppress_tokens: Optional[List[int]] = [-1],
                    without_timestamps: bool = False, max_initial_timestamp: float = 1.0, word_timestamps: bool = False,
                    prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
-                   multilingual: bool = False, vad_filter: bool = False, vad_parameters=None,
+                   multilingual: Optional[bool] = None, vad_filter: bool = False, vad_parameters=None,
                    max_new_tokens: Optional[int] = None, chunk_length: Optional[int] = None,
                    clip_timestamps: Union[str, List[float]] = "0", hallucination_silence_threshold: Optional[float] = None,
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
@@ -466,6 +514,20 @@ class WhisperModel:
                    max_line_count: Optional[int] = None, max_cue_seconds: Optional[float] = None,
                    language_candidates: Optional[Sequence[str]] = None):
         """faster-whisper's `WhisperModel.transcribe`, plus these arguments of this engine:
+
+        multilingual: faster-whisper's code-switching option.  True: every 30 s window is decoded under the language
+        detected for that window instead of the file's.  The detection runs on the device inside the window's first
+        decode (wm_generate_multilingual: one decoder step from <|startoftranscript|>, the language head, and a kernel
+        that writes the chosen language token into the prompt before the prefill), once per window and before the
+        fallback temperatures, which then decode with that language; word alignment uses its sot sequence and the next
+        window's prompt starts from it.  language_candidates confines the per-window detection too.  info.language,
+        info.language_probability and info.all_language_probs keep their meaning (the file-level detection, which is
+        also where the first window starts from); every Segment carries `language`, its window's code (None with the
+        option off).  A call that names its `language` asks for it in every window: multilingual=True with it raises
+        NotImplementedError, as before.  None reads VLOG_AMD_MULTILINGUAL (0 / 1, default off; ignored, and logged
+        once, by a call that names its language); an English-only model turns the option off and logs that once.  What is in force is echoed in
+        info.transcription_options.multilingual.  Every decode form takes it: sections=N, transcribe_many and
+        throughput mode.  Measurement: DESIGN.md §8.
 
         language_candidates: the language codes this deployment serves, e.g. ["en", "es", "de"].  Used only when
         `language` is None and the model is multilingual (otherwise ignored; the English-only case is logged once):
@@ -532,10 +594,10 @@ class WhisperModel:
         VLOG_AMD_LOCKSTEP_FALLBACK environment variable (0 / 1), else False.  Echoed in
         info.transcription_options.lockstep_fallback.  Throughput mode has its own batched re-decode and ignores it.
         Measurement: DESIGN.md §8 (tools/bench_worker_call.py --lockstep-fallback)."""
-        for name, val, default in (("multilingual", multilingual, False),
-                                   ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
-            if val != default:
-                raise NotImplementedError(f"{name}={val!r} is not supported by the MI355X engine")
+        if hallucination_silence_threshold is not None:
+            raise NotImplementedError(f"hallucination_silence_threshold={hallucination_silence_threshold!r} is not "
+                                      "supported by the MI355X engine")
+        multilingual = self._multilingual(multilingual, [language])
         if chunk_length not in (None, CHUNK_LENGTH):
             raise NotImplementedError("chunk_length other than 30 s is not supported")
         if task not in ("transcribe", "translate"):
@@ -572,7 +634,7 @@ class WhisperModel:
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
                 language_detection_segments=language_detection_segments, sequence_bias=sequence_bias,
-                language_candidates=language_candidates, **captions)
+                language_candidates=language_candidates, multilingual=multilingual, **captions)
         if sections > 1 and not isinstance(audio, np.ndarray):
             audio = self._load_audio(audio)     # (the cuts without VAD are chosen on the samples)
         features, tokenizer, options, info, speech_chunks = self._prepare_file(
@@ -692,11 +754,15 @@ class WhisperModel:
                                  prefix, hotwords)
 
     def _generate(self, prompt: List[int], options: TranscriptionOptions, temperature: float, max_length: int,
-                  seed: int, slot: int = 0) -> _GenOut:
+                  seed: int, slot: int = 0, lang_pos: int = -1) -> _GenOut:
+        """One window's decode at one temperature.  lang_pos >= 0 (multilingual=True, the window's first decode): the
+        engine identifies the window and decodes it under that language in the same call (wm_generate_multilingual;
+        the prompt holds a placeholder at lang_pos); the result names the language."""
         st = self.dims.specials
         mit = int(round(options.max_initial_timestamp / self.time_precision))
         sampling = temperature > 0
-        res, _ = self.engine.generate(
+        kw = dict(language_auto=self._language_auto(options, [lang_pos])) if lang_pos >= 0 else {}
+        res, *lang = self.engine.generate(
             [slot], [prompt], beam_size=1 if sampling else options.beam_size, patience=options.patience,
             length_penalty=options.length_penalty, max_length=max_length, temperature=temperature,
             num_hypotheses=options.best_of if sampling else 1, seed=seed, suppress_tokens=options.suppress_tokens,
@@ -704,9 +770,10 @@ class WhisperModel:
             with_timestamps=not options.without_timestamps,
             sot_index=prompt.index(st.sot) if st.sot in prompt else -1, check_every=4,
             repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size,
-            sequence_bias=options.sequence_bias_table)
+            sequence_bias=options.sequence_bias_table, **kw)
         r = res[0]
-        return _GenOut(r.tokens, r.score, r.no_speech_prob)
+        return _GenOut(r.tokens, r.score, r.no_speech_prob,
+                       st.lang_codes[int(lang[1][0][0])] if lang_pos >= 0 else None)
 
     def generate_with_fallback(self, prompt: List[int], tokenizer: Tokenizer, options: TranscriptionOptions,
                                seed: int = 0, slot: int = 0, first: Optional[_GenOut] = None):
@@ -734,8 +801,15 @@ class WhisperModel:
             with self._lock:
                 self._use_cross_form(options.beam_size)
                 self._encode(features, req.seek, req.size, 0)
-                decode = self.generate_with_fallback(req.prompt, tokenizer, options, seed=req.window)
-                out = state.consume(decode, lambda current, size, last: self.add_word_timestamps(
+                first = None
+                if state.multilingual and options.temperatures:
+                    # the window's language is detected once, inside its first decode; the fallback temperatures
+                    # then run with the prompt that carries it
+                    first = self._generate(req.prompt, options, options.temperatures[0], req.max_length, req.window,
+                                           lang_pos=req.lang_pos)
+                    state.set_window_language(first.language)
+                decode = self.generate_with_fallback(req.prompt, tokenizer, options, seed=req.window, first=first)
+                out = state.consume(decode, lambda current, size, last, tokenizer=tokenizer: self.add_word_timestamps(
                     [current], tokenizer, size, options.prepend_punctuations, options.append_punctuations, last))
             for d in out:
                 yield self._segment(d)
@@ -778,20 +852,27 @@ class WhisperModel:
                 enc = self.engine.encode(mel, [i * N_FRAMES for i in range(nb)], [req.size for _, _, req in batch])
             self.engine.cross_kv(enc, 0)
 
-            def shared_pass(idx, t, seeds=None):
+            def shared_pass(idx, t, seeds=None, auto=False):
                 """entries idx decoded together at temperature t, one generate per suppress list; seeds (sampling):
-                one per entry, so every window draws as in a call of its own (engine.generate seeds)"""
+                one per entry, so every window draws as in a call of its own (engine.generate seeds).  auto (the first
+                pass of a multilingual round): the entries with the option on choose their language in the call"""
                 out: List[Optional[_GenOut]] = [None] * len(idx)
                 groups: dict = {}
-                for k, i in enumerate(idx):     # the suppress list is one per generate call
-                    groups.setdefault(tuple(batch[i][1].options.suppress_tokens), []).append(k)
-                for sup, ks in groups.items():
+                for k, i in enumerate(idx):     # the suppress list is one per generate call, and so is the language mask
+                    o = batch[i][1].options
+                    mask = o.language_candidates if auto and batch[i][2].lang_pos >= 0 else None
+                    groups.setdefault((tuple(o.suppress_tokens), mask), []).append(k)
+                for (sup, _), ks in groups.items():
                     members = [idx[k] for k in ks]
                     prompts = [batch[i][2].prompt for i in members]
                     kw = {}
                     if t > 0:                   # the arguments _generate passes for a sampled decode
                         kw = dict(num_hypotheses=opt0.best_of, seeds=[seeds[k] for k in ks])
-                    res, _ = self.engine.generate(
+                    pos = [batch[i][2].lang_pos if auto else -1 for i in members]
+                    if any(p >= 0 for p in pos):
+                        first_auto = members[next(j for j, p in enumerate(pos) if p >= 0)]
+                        kw["language_auto"] = self._language_auto(batch[first_auto][1].options, pos)
+                    res, *lang = self.engine.generate(
                         members, prompts, beam_size=1 if t > 0 else opt0.beam_size, patience=opt0.patience,
                         length_penalty=opt0.length_penalty, max_length=[batch[i][2].max_length for i in members],
                         temperature=t, suppress_tokens=list(sup),
@@ -800,34 +881,46 @@ class WhisperModel:
                         sot_index=[p.index(sot) if sot in p else -1 for p in prompts], check_every=4,
                         repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size,
                         sequence_bias=opt0.sequence_bias_table, **kw)
-                    for k, r in zip(ks, res):
+                    for j, (k, r) in enumerate(zip(ks, res)):
                         out[k] = _GenOut(r.tokens, r.score, r.no_speech_prob)
+                        if pos[j] >= 0:
+                            out[k].language = self.dims.specials.lang_codes[int(lang[1][0][j])]
                 return out
 
             def first_pass(idx):
                 if sampling and levels:
-                    return shared_pass(idx, t0, [batch[i][2].window for i in idx])
+                    return shared_pass(idx, t0, [batch[i][2].window for i in idx], auto=True)
                 if sampling:
                     # a sampled pass draws noise keyed on (seed, hypothesis index): a file's draws would depend on
                     # its place in the round, so each window decodes alone, with generate_with_fallback's call
                     return [self._generate(batch[i][2].prompt, batch[i][1].options, t0, batch[i][2].max_length,
-                                           batch[i][2].window, slot=i) for i in idx]
-                return shared_pass(idx, t0)
+                                           batch[i][2].window, slot=i, lang_pos=batch[i][2].lang_pos) for i in idx]
+                return shared_pass(idx, t0, auto=True)
 
             def fallback_generate(i, t, seed):
                 _, state, req = batch[i]
                 return self._generate(req.prompt, state.options, t, req.max_length, seed, slot=i)
 
-            def align(i, current, size, last):
+            def align(i, current, size, last, tokenizer=None):
+                # (a round without multilingual: one wm_align_batch per item, as before)
                 _, state, _ = batch[i]
                 o = state.options
-                return self.add_word_timestamps([current], state.tokenizer, size, o.prepend_punctuations,
+                return self.add_word_timestamps([current], tokenizer or state.tokenizer, size, o.prepend_punctuations,
                                                 o.append_punctuations, last, slots=[i])
 
+            def align_group(items):
+                # a multilingual round: the items of one language in ONE wm_align_batch, each against its own slot and
+                # with its own last-speech time (items: seek_state.consume_round_grouped)
+                return self.add_word_timestamps([it[1] for it in items], items[0][4], [it[2] for it in items],
+                                                opt0.prepend_punctuations, opt0.append_punctuations,
+                                                [it[3] for it in items], slots=[it[0] for it in items])
+
             if levels:
-                decode_round_levels(batch, first_pass, shared_pass, align if opt0.word_timestamps else None, emit)
+                decode_round_levels(batch, first_pass, shared_pass, align if opt0.word_timestamps else None, emit,
+                                    align_group)
             else:
-                decode_round_with(batch, first_pass, fallback_generate, align if opt0.word_timestamps else None, emit)
+                decode_round_with(batch, first_pass, fallback_generate, align if opt0.word_timestamps else None, emit,
+                                  align_group)
 
     def _generate_sections(self, features: torch.Tensor, tokenizer: Tokenizer, options: TranscriptionOptions,
                            bounds: Sequence[Tuple[int, int]], in_flight: int):
@@ -873,7 +966,7 @@ class WhisperModel:
                         suppress_blank: bool = True, suppress_tokens: Optional[List[int]] = [-1],
                         without_timestamps: bool = False, max_initial_timestamp: float = 1.0,
                         word_timestamps: bool = False, prepend_punctuations: str = "\"'“¿([{-",
-                        append_punctuations: str = "\"'.。,，!！?？:：”)]}、", multilingual: bool = False,
+                        append_punctuations: str = "\"'.。,，!！?？:：”)]}、", multilingual: Optional[bool] = None,
                         vad_filter: bool = False, vad_parameters=None, max_new_tokens: Optional[int] = None,
                         chunk_length: Optional[int] = None, clip_timestamps: Union[str, List[float]] = "0",
                         hallucination_silence_threshold: Optional[float] = None, hotwords=None,
@@ -912,10 +1005,10 @@ class WhisperModel:
         language_candidates (see `transcribe`): ONE sequence of codes for all files, in force for every file whose
         language is None; a per-file list of lists raises ValueError.
         With throughput mode on, this is BatchedInferencePipeline.transcribe_many."""
-        for name, val, default in (("multilingual", multilingual, False),
-                                   ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
-            if val != default:
-                raise NotImplementedError(f"{name}={val!r} is not supported by the MI355X engine")
+        if hallucination_silence_threshold is not None:
+            raise NotImplementedError(f"hallucination_silence_threshold={hallucination_silence_threshold!r} is not "
+                                      "supported by the MI355X engine")
+        multilingual = self._multilingual(multilingual, language if isinstance(language, (list, tuple)) else [language])
         if chunk_length not in (None, CHUNK_LENGTH):
             raise NotImplementedError("chunk_length other than 30 s is not supported")
         if task not in ("transcribe", "translate"):
@@ -956,7 +1049,7 @@ class WhisperModel:
                 append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
                 max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
                 language_detection_segments=language_detection_segments, sequence_bias=sequence_bias,
-                language_candidates=language_candidates, **captions)
+                language_candidates=language_candidates, multilingual=multilingual, **captions)
 
         files: dict = {}
         results: List[List[Segment]] = [[] for _ in range(n)]
@@ -1105,9 +1198,12 @@ class WhisperModel:
                             slots: Optional[Sequence[int]] = None) -> float:
         """faster-whisper add_word_timestamps: segment group i (one window's segments) is aligned against the
         encoder output in slot slots[i] with num_frames[i] frames (BatchedInferencePipeline passes one group
-        per window of a batch)."""
+        per window of a batch).  last_speech_timestamp: one time threaded through the groups in order, or a list with
+        one time per group (groups of different files or sections, aligned in one call: each keeps its own) -> a list."""
+        per_group = isinstance(last_speech_timestamp, (list, tuple))
+        lasts = list(last_speech_timestamp) if per_group else None
         if len(segments) == 0:
-            return last_speech_timestamp
+            return lasts if per_group else last_speech_timestamp
         text_tokens, per_seg = [], []
         for segment in segments:
             st = [[t for t in sub["tokens"] if t < tokenizer.eot] for sub in segment]
@@ -1134,6 +1230,8 @@ class WhisperModel:
             wi = 0
             time_offset = segment[0]["seek"] / self.frames_per_second
             med, mx = med_max[si]
+            if per_group:
+                last_speech_timestamp = lasts[si]
             for ssi, sub in enumerate(segment):
                 saved = 0
                 words = []
@@ -1163,7 +1261,9 @@ class WhisperModel:
                         sub["end"] = words[-1]["end"]
                     last_speech_timestamp = sub["end"]
                 segments[si][ssi]["words"] = words
-        return last_speech_timestamp
+            if per_group:
+                lasts[si] = last_speech_timestamp
+        return lasts if per_group else last_speech_timestamp
 
 
 @dataclass
@@ -1178,6 +1278,7 @@ class WindowResult:
     compression_ratio: float
     no_speech_prob: float
     segments: Optional[List[dict]] = None      # split (and, with word timestamps, word-aligned) segments
+    language: Optional[str] = None             # multilingual=True: the language detected for the window
 
 
 class BatchedInferencePipeline:
@@ -1278,12 +1379,25 @@ class BatchedInferencePipeline:
                 pending = list(range(len(wins)))
                 results: dict = {}
                 tries: dict = {i: [] for i in pending}
+                # multilingual: the first temperature's call keeps the one shared prompt and every window chooses its
+                # language in it (one position for all); later temperatures pass per-window prompts, of one length
+                # still, that carry the returned tokens
+                auto = bool(options.multilingual) and tokenizer.language is not None
+                lang_pos = prompt.index(st.sot) + 1
+                win_lang: dict = {}
                 for ti, T in enumerate(options.temperatures):
                     if not pending:
                         break
                     sampling = T > 0
-                    res, _ = eng.generate(
-                        pending, [prompt] * len(pending), beam_size=1 if sampling else options.beam_size,
+                    prompts = [prompt] * len(pending)
+                    kw = {}
+                    if auto and ti == 0:
+                        kw["language_auto"] = m._language_auto(options, [lang_pos] * len(pending))
+                    elif auto:
+                        prompts = [prompt[:lang_pos] + [tokenizer.for_language(win_lang[i]).language] +
+                                   prompt[lang_pos + 1:] for i in pending]
+                    res, *lang = eng.generate(
+                        pending, prompts, beam_size=1 if sampling else options.beam_size,
                         patience=options.patience, length_penalty=options.length_penalty, max_length=max_length,
                         temperature=T, num_hypotheses=options.best_of if sampling else 1, seed=seed + 7919 * ti + b0,
                         suppress_tokens=options.suppress_tokens, suppress_blank=options.suppress_blank,
@@ -1291,7 +1405,9 @@ class BatchedInferencePipeline:
                         sot_index=prompt.index(st.sot), check_every=4, compact=self.compact,
                         repetition_penalty=options.repetition_penalty,
                         no_repeat_ngram_size=options.no_repeat_ngram_size,
-                        sequence_bias=options.sequence_bias_table)
+                        sequence_bias=options.sequence_bias_table, **kw)
+                    if auto and ti == 0:
+                        win_lang = {i: st.lang_codes[int(t)] for i, t in zip(pending, lang[1][0])}
                     still = []
                     for i, r in zip(pending, res):
                         alp = segs.avg_logprob(r.score, len(r.tokens), options.length_penalty)
@@ -1312,21 +1428,26 @@ class BatchedInferencePipeline:
                 for i, (s, n) in enumerate(wins):
                     r, alp, T, cr = results[i]
                     sb = seek_bases[b0 + i] if seek_bases is not None else 0
-                    wr = WindowResult(b0 + i, s - sb, n, time_offsets[b0 + i], r.tokens, alp, T, cr, r.no_speech_prob)
+                    wr = WindowResult(b0 + i, s - sb, n, time_offsets[b0 + i], r.tokens, alp, T, cr, r.no_speech_prob,
+                                      language=win_lang.get(i))
                     wr.segments = self.window_segments(wr, tokenizer, options)
                     batch.append(wr)
                 if options.word_timestamps:
                     # the batch's encoder outputs are still in slots 0..B-1: one batched alignment for every
                     # window with text (faster-whisper aligns a whole batch of segments in one model.align); with
-                    # several files, one call per file so each keeps its own last-speech time
+                    # several files, one call per file so each keeps its own last-speech time; multilingual: inside a
+                    # file one call per run of windows of one language (wm_align_batch takes one sot sequence), in
+                    # window order, so the last-speech time still runs through the file's windows in order
                     fid = [files[b0 + i] if files is not None else 0 for i in range(len(batch))]
                     for f in sorted(set(fid)):
                         idx = [i for i, wr in enumerate(batch) if wr.segments and fid[i] == f]
-                        if idx:
+                        for lang_code, run in itertools.groupby(idx, key=lambda i: batch[i].language):
+                            run = list(run)
                             last_speech[f] = m.add_word_timestamps(
-                                [batch[i].segments for i in idx], tokenizer, [batch[i].size for i in idx],
-                                options.prepend_punctuations, options.append_punctuations,
-                                last_speech.get(f, 0.0), slots=idx)
+                                [batch[i].segments for i in run],
+                                tokenizer.for_language(lang_code) if lang_code else tokenizer,
+                                [batch[i].size for i in run], options.prepend_punctuations,
+                                options.append_punctuations, last_speech.get(f, 0.0), slots=run)
                 out.extend(batch)
         return out
 
@@ -1353,7 +1474,7 @@ class BatchedInferencePipeline:
                    suppress_blank: bool = True, suppress_tokens: Optional[List[int]] = [-1],
                    without_timestamps: bool = True, max_initial_timestamp: float = 1.0, word_timestamps: bool = False,
                    prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
-                   multilingual: bool = False, vad_filter: bool = True, vad_parameters=None,
+                   multilingual: Optional[bool] = None, vad_filter: bool = True, vad_parameters=None,
                    max_new_tokens: Optional[int] = None, chunk_length: Optional[int] = None, clip_timestamps=None,
                    hallucination_silence_threshold: Optional[float] = None, batch_size: int = 16,
                    hotwords: Optional[str] = None, language_detection_threshold: Optional[float] = 0.5,
@@ -1365,10 +1486,10 @@ class BatchedInferencePipeline:
         language_candidates: as WhisperModel.transcribe (the whitelist of the file's language detection).
         max_line_width, max_line_count, max_cue_seconds: caption shaping as in WhisperModel.transcribe; the windows
         then decode as with word_timestamps=True and the segments leave through captions.shape_captions."""
-        for name, val, default in (("multilingual", multilingual, False),
-                                   ("hallucination_silence_threshold", hallucination_silence_threshold, None)):
-            if val != default:
-                raise NotImplementedError(f"{name}={val!r} is not supported by the MI355X engine")
+        if hallucination_silence_threshold is not None:
+            raise NotImplementedError(f"hallucination_silence_threshold={hallucination_silence_threshold!r} is not "
+                                      "supported by the MI355X engine")
+        multilingual = self.model._multilingual(multilingual, [language])
         if prefix is not None:       # every window of a batch shares one prompt length; a prefix belongs to the first only
             raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
         captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
@@ -1387,7 +1508,7 @@ class BatchedInferencePipeline:
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
             append_punctuations=append_punctuations, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
             sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias), captions=captions,
-            language_candidates=prep["language_candidates"])
+            language_candidates=prep["language_candidates"], multilingual=multilingual)
         windows = prep["windows"]
         offsets = [s * HOP_LENGTH / SAMPLE_RATE for s, _ in windows]
         results = self.decode_windows(prep["features"], windows, offsets, tokenizer, options, last_speech={})
@@ -1418,6 +1539,8 @@ class BatchedInferencePipeline:
         if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
             raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
         language_candidates = self.model._language_candidates(kw.pop("language_candidates", None)) or ()
+        kw["multilingual"] = self.model._multilingual(kw.pop("multilingual", None),
+                                                      language if isinstance(language, (list, tuple)) else [language])
         langs = list(language) if isinstance(language, (list, tuple)) else [language] * n
         if len(langs) != n:
             raise ValueError("one language per file")
@@ -1506,7 +1629,8 @@ class BatchedInferencePipeline:
                  max_new_tokens: Optional[int] = None, clip_timestamps=None, repetition_penalty: float = 1,
                  no_repeat_ngram_size: int = 0, hotwords: Optional[str] = None,
                  sequence_bias=(None, None), captions: Optional[dict] = None,
-                 language_candidates: Optional[Tuple[str, ...]] = None) -> TranscriptionOptions:
+                 language_candidates: Optional[Tuple[str, ...]] = None,
+                 multilingual: bool = False) -> TranscriptionOptions:
         """sequence_bias: (the mapping in force, the engine's table), WhisperModel._sequence_bias' pair; captions:
         _caption_options' dict (word_timestamps is the caller's, set from it already)"""
         on = captions if captions and captions["max_line_width"] else {}
@@ -1521,7 +1645,7 @@ class BatchedInferencePipeline:
             suppress_tokens=list(tokenizer.suppressed_tokens(suppress_tokens)) if suppress_tokens else [],
             without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
             word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-            append_punctuations=append_punctuations, multilingual=False, max_new_tokens=max_new_tokens,
+            append_punctuations=append_punctuations, multilingual=bool(multilingual), max_new_tokens=max_new_tokens,
             clip_timestamps=clip_timestamps or "0", hallucination_silence_threshold=None, hotwords=hotwords,
             sequence_bias=sequence_bias[0], sequence_bias_table=sequence_bias[1],
             max_line_width=on.get("max_line_width"), max_line_count=on.get("max_line_count"),
@@ -1550,7 +1674,8 @@ class BatchedInferencePipeline:
                 yield Segment(id=idx, seek=wr.seek, start=s["start"], end=s["end"], text=text, tokens=s["tokens"],
                               avg_logprob=wr.avg_logprob, compression_ratio=wr.compression_ratio,
                               no_speech_prob=wr.no_speech_prob, temperature=wr.temperature,
-                              words=[_word(w) for w in s["words"]] if options.word_timestamps else None)
+                              words=[_word(w) for w in s["words"]] if options.word_timestamps else None,
+                              language=wr.language)
 
 
 def default_batched_options(**kw) -> dict:
