@@ -23,12 +23,14 @@ with vlog_amd/shard.py.
 """
 from __future__ import annotations
 
+import inspect
 import itertools
 import logging
 import os
 import threading
-from dataclasses import asdict, dataclass, field
-from typing import BinaryIO, Iterable, List, Mapping, Optional, Sequence, Tuple, Union
+import types
+from dataclasses import MISSING, asdict, dataclass, fields
+from typing import Any, BinaryIO, Iterable, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -197,20 +199,200 @@ def _word(w: dict) -> Word:
     return word
 
 
-def _caption_options(max_line_width, max_line_count, max_cue_seconds) -> dict:
-    """The caption arguments of a transcribe call -> the keyword arguments that carry them on, resolved against the
-    environment once: the three TranscriptionOptions fields, and word_timestamps=True when shaping is on."""
-    caps = resolve_caption_options(max_line_width, max_line_count, max_cue_seconds, os.environ)
-    if caps is None:
-        return dict(max_line_width=0)
-    return dict(max_line_width=caps[0], max_line_count=caps[1], max_cue_seconds=caps[2], word_timestamps=True)
-
-
 def _shaped(segments, options: TranscriptionOptions):
     """The last stage of every segment stream: shape_captions when the options have it on."""
     if not options.max_line_width:
         return segments
     return shape_captions(segments, options.max_line_width, options.max_line_count, options.max_cue_seconds)
+
+
+def _finished(segments, speech_chunks, options: Optional[TranscriptionOptions] = None):
+    """The tail of a sequential segment stream: the VAD's times restored to file time, then caption shaping
+    (options None: align, which does not shape)."""
+    if speech_chunks:
+        from .vad import restore_speech_timestamps
+        segments = restore_speech_timestamps(segments, speech_chunks, SAMPLE_RATE)
+    return segments if options is None else _shaped(segments, options)
+
+
+def _vad_options(vad_parameters) -> VadOptions:
+    return vad_parameters if isinstance(vad_parameters, VadOptions) else VadOptions(**(vad_parameters or {}))
+
+
+def _decode_kwargs(options: TranscriptionOptions, temperature: float) -> dict:
+    """The engine.generate keyword arguments that every decode form takes from the options at one temperature.  The
+    call sites add what is theirs: slots, prompts, max_length, sot_index, the suppress list, seed or seeds,
+    num_hypotheses, compact, language_auto."""
+    return dict(beam_size=1 if temperature > 0 else options.beam_size, patience=options.patience,
+                length_penalty=options.length_penalty, temperature=temperature, suppress_blank=options.suppress_blank,
+                max_initial_timestamp_index=int(round(options.max_initial_timestamp / TIME_PRECISION)),
+                with_timestamps=not options.without_timestamps, check_every=4,
+                repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size,
+                sequence_bias=options.sequence_bias_table)
+
+
+@dataclass
+class _File:
+    """One file before its decode: the log-mel, its language and what TranscriptionInfo reports.  speech_chunks: the
+    VAD chunks the sequential path collected (None: no VAD); windows: the throughput path's (seek, size) ranges."""
+    features: torch.Tensor
+    duration: float
+    duration_after_vad: float
+    vad_options: Optional[VadOptions]
+    language: str
+    language_probability: float
+    all_language_probs: Optional[List[Tuple[str, float]]]
+    language_candidates: Optional[Tuple[str, ...]]      # the whitelist in force for this file (None: off, or named)
+    speech_chunks: Optional[List[dict]] = None
+    windows: Optional[List[Tuple[int, int]]] = None
+
+    def info(self, options: TranscriptionOptions) -> TranscriptionInfo:
+        return TranscriptionInfo(language=self.language, language_probability=self.language_probability,
+                                 duration=self.duration, duration_after_vad=self.duration_after_vad,
+                                 all_language_probs=self.all_language_probs, transcription_options=options,
+                                 vad_options=self.vad_options)
+
+
+_NO_CLIPS = ("0", [0], [0.0])           # the clip_timestamps values that clip nothing
+_PER_FILE = ("language", "initial_prompt", "hotwords", "prefix")
+
+
+@dataclass(frozen=True)
+class _Call:
+    """A public transcribe call after validation and environment resolution (_resolve_call): built once, at the top
+    of the entry point, and handed on as it is (to the throughput pipeline too).
+    args: every argument by its public name, as resolved: multilingual, lockstep_fallback and sections as in force;
+    language_candidates the call's tuple or None; max_line_width / max_line_count / max_cue_seconds as in force (None:
+    shaping off) with word_timestamps forced on by them; language, initial_prompt, hotwords and prefix as lists with one
+    value per file (one file: one value).
+    throughput: the options are BatchedInferencePipeline's (no text conditioning, no prefix, no clips)."""
+    args: Mapping[str, Any]
+    throughput: bool
+
+    def options(self, model: "WhisperModel", tokenizer: Tokenizer, f: int = 0,
+                language_candidates: Optional[Tuple[str, ...]] = None) -> TranscriptionOptions:
+        """The TranscriptionOptions of file f under `tokenizer` (the suppress list and the sequence-bias table depend on
+        it).  Where each field comes from:
+          * a field with the name of an argument of the call is that argument as resolved: the plain decode options,
+            and multilingual, lockstep_fallback, word_timestamps and the three caption fields as in force.  A new
+            option that TranscriptionOptions echoes under its own name needs nothing here; a field that shares its
+            name with an argument of ANOTHER meaning must be set explicitly below;
+          * derived below: temperatures (from `temperature`), suppress_tokens and the sequence-bias pair (both through
+            the tokenizer), the per-file initial_prompt / prefix / hotwords, and the file's language_candidates;
+          * section_frames is set by `transcribe` once the sections are planned;
+          * BatchedInferencePipeline's entry points have no condition_on_previous_text, prompt_reset_on_temperature
+            or lockstep_fallback argument: the throughput block sets them, with the other constants of that mode,
+            and overrides what a WhisperModel call in throughput mode passed for them."""
+        a = self.args
+        o = {fd.name: a[fd.name] for fd in fields(TranscriptionOptions) if fd.name in a}
+        t, sup = a["temperature"], a["suppress_tokens"]
+        o["sequence_bias"], o["sequence_bias_table"] = model._sequence_bias(tokenizer, a["sequence_bias"])
+        o.update(temperatures=list(t) if isinstance(t, (list, tuple)) else [t],
+                 suppress_tokens=list(tokenizer.suppressed_tokens(sup)) if sup else [],
+                 initial_prompt=a["initial_prompt"][f], prefix=a["prefix"][f], hotwords=a["hotwords"][f],
+                 language_candidates=language_candidates or None)
+        if self.throughput:
+            o.update(condition_on_previous_text=False, prompt_reset_on_temperature=0.5, prefix=None,
+                     hallucination_silence_threshold=None, clip_timestamps=a["clip_timestamps"] or "0",
+                     lockstep_fallback=False)       # (throughput mode has its own batched re-decode)
+        return TranscriptionOptions(**o)
+
+
+def _resolve_call(model: "WhisperModel", entry: str, args: Mapping[str, Any], n_files: Optional[int] = None) -> _Call:
+    """The one resolver of the four public entry points.  entry: "transcribe" / "transcribe_many" (WhisperModel) or
+    "batched" / "batched_many" (BatchedInferencePipeline); args: the entry point's arguments by name (its locals());
+    n_files: len(audios) of a _many entry.  Every check and every environment default of a call lives here; the
+    checks run in the order each entry point has always run them (`order` below), so a call with two mistakes keeps
+    reporting the same one."""
+    a = {k: v for k, v in args.items() if k not in ("self", "audio", "audios", "kw")}
+    many, batched = n_files is not None, entry.startswith("batched")
+    n = n_files if many else 1
+
+    def hallucination():
+        if a["hallucination_silence_threshold"] is not None:
+            raise NotImplementedError(f"hallucination_silence_threshold={a['hallucination_silence_threshold']!r} is "
+                                      "not supported by the MI355X engine")
+
+    def multilingual():
+        named = a["language"]
+        a["multilingual"] = model._multilingual(
+            a["multilingual"], named if many and isinstance(named, (list, tuple)) else [named])
+
+    def chunk_length():
+        if a["chunk_length"] not in (None, CHUNK_LENGTH):
+            raise NotImplementedError("chunk_length other than 30 s is not supported")
+
+    def task():
+        if a["task"] not in ("transcribe", "translate"):
+            raise ValueError(f"unknown task {a['task']!r}")
+
+    def sections():
+        if a["sections"] is None:
+            a["sections"] = int(os.environ.get("VLOG_AMD_SECTIONS", "") or 1)
+        if not 1 <= a["sections"] <= MAX_SECTIONS:
+            raise ValueError(f"sections must be between 1 and {MAX_SECTIONS}, got {a['sections']}")
+        if a["sections_in_flight"] is not None and a["sections_in_flight"] < 1:
+            raise ValueError("sections_in_flight must be >= 1")
+        if a["sections"] > 1 and model.throughput:
+            raise ValueError("sections > 1 is the sequential mode's; throughput mode cuts the file its own way")
+        if a["sections"] > 1 and a["clip_timestamps"] not in _NO_CLIPS:
+            raise ValueError("sections > 1 cannot be combined with clip_timestamps")
+
+    def max_files():
+        if a["max_files"] < 1:
+            raise ValueError("max_files must be >= 1")
+
+    def one_bias():
+        if a["sequence_bias"] is not None and not isinstance(a["sequence_bias"], Mapping):
+            raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
+
+    def lockstep_fallback():
+        a["lockstep_fallback"] = _resolve_lockstep_fallback(a["lockstep_fallback"])
+
+    def captions():
+        caps = resolve_caption_options(a["max_line_width"], a["max_line_count"], a["max_cue_seconds"], os.environ)
+        a["max_line_width"], a["max_line_count"], a["max_cue_seconds"] = caps or (None, None, None)
+        if caps:
+            a["word_timestamps"] = True         # the shaper needs word times
+
+    def candidates():
+        a["language_candidates"] = model._language_candidates(a["language_candidates"])
+
+    def per_file():
+        for name in _PER_FILE:
+            v = a[name]
+            # (a list as the initial prompt of ONE call, or of the pipeline's transcribe_many, is token ids)
+            if many and isinstance(v, (list, tuple)) and (name == "language" or not batched):
+                if len(v) != n:
+                    raise ValueError("one language per file" if batched else
+                                     f"{name}: one value per file expected ({n}), got {len(v)}")
+                a[name] = list(v)
+            else:
+                a[name] = [v] * n
+
+    def no_prefix():        # every window of a batch shares one prompt length; a prefix belongs to the first only
+        if a["prefix"] is not None:
+            raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
+
+    def throughput_forward():
+        if not model.throughput:
+            return
+        if any(p is not None for p in a["initial_prompt"]) or a["clip_timestamps"] not in _NO_CLIPS or \
+                any(p is not None for p in a["prefix"]):
+            raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
+        if len(set(a["hotwords"])) > 1:
+            raise NotImplementedError("per-file hotwords in throughput mode")
+        a["clip_timestamps"] = None             # (nothing is clipped: the pipeline's own default)
+
+    order = {"transcribe": (hallucination, multilingual, chunk_length, task, sections, lockstep_fallback, captions,
+                            candidates, per_file, throughput_forward),
+             "transcribe_many": (hallucination, multilingual, chunk_length, task, max_files, one_bias,
+                                 lockstep_fallback, captions, candidates, per_file, throughput_forward),
+             "batched": (hallucination, multilingual, no_prefix, captions, candidates, per_file),
+             "batched_many": (no_prefix, captions, one_bias, candidates, multilingual, per_file)}
+    for check in order[entry]:
+        check()
+    return _Call(args=types.MappingProxyType(a), throughput=batched or model.throughput)
 
 
 def _resolve_device_index(device: str, device_index) -> int:
@@ -464,8 +646,7 @@ class WhisperModel:
         speech_chunks = None
         if vad_filter:
             from .vad import collect_chunks, get_speech_timestamps
-            vad_opts = vad_parameters if isinstance(vad_parameters, VadOptions) else VadOptions(**(vad_parameters or {}))
-            speech_chunks = get_speech_timestamps(audio, vad_opts, self)
+            speech_chunks = get_speech_timestamps(audio, _vad_options(vad_parameters), self)
             if not speech_chunks:
                 return []
             audio = collect_chunks(audio, speech_chunks)
@@ -594,77 +775,26 @@ class WhisperModel:
         VLOG_AMD_LOCKSTEP_FALLBACK environment variable (0 / 1), else False.  Echoed in
         info.transcription_options.lockstep_fallback.  Throughput mode has its own batched re-decode and ignores it.
         Measurement: DESIGN.md §8 (tools/bench_worker_call.py --lockstep-fallback)."""
-        if hallucination_silence_threshold is not None:
-            raise NotImplementedError(f"hallucination_silence_threshold={hallucination_silence_threshold!r} is not "
-                                      "supported by the MI355X engine")
-        multilingual = self._multilingual(multilingual, [language])
-        if chunk_length not in (None, CHUNK_LENGTH):
-            raise NotImplementedError("chunk_length other than 30 s is not supported")
-        if task not in ("transcribe", "translate"):
-            raise ValueError(f"unknown task {task!r}")
-        if sections is None:
-            sections = int(os.environ.get("VLOG_AMD_SECTIONS", "") or 1)
-        if not 1 <= sections <= MAX_SECTIONS:
-            raise ValueError(f"sections must be between 1 and {MAX_SECTIONS}, got {sections}")
-        if sections_in_flight is not None and sections_in_flight < 1:
-            raise ValueError("sections_in_flight must be >= 1")
-        if sections > 1 and self.throughput:
-            raise ValueError("sections > 1 is the sequential mode's; throughput mode cuts the file its own way")
-        if sections > 1 and clip_timestamps not in ("0", [0], [0.0]):
-            raise ValueError("sections > 1 cannot be combined with clip_timestamps")
-        lockstep_fallback = _resolve_lockstep_fallback(lockstep_fallback)
-        captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
-        word_timestamps = captions.pop("word_timestamps", word_timestamps)
-        language_candidates = self._language_candidates(language_candidates, language) or ()
+        args = dict(locals())
+        call = _resolve_call(self, "transcribe", args)
         if self.throughput:
             # opt-in throughput mode for the UNCHANGED worker (VLOG_AMD_THROUGHPUT=1): its call
             # transcribe(wav, language, task, beam_size=5, vad_filter=True) runs as BatchedInferencePipeline:
             # VAD-bounded windows decoded independently in large batches (no previous-text prompt), with
             # timestamps kept so the worker's WebVTT still gets per-segment times.
-            if initial_prompt is not None or clip_timestamps not in ("0", [0], [0.0]) or prefix is not None:
-                raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
-            return self._pipeline().transcribe(
-                audio, language=language, task=task, beam_size=beam_size, best_of=best_of, patience=patience,
-                length_penalty=length_penalty, repetition_penalty=repetition_penalty,
-                no_repeat_ngram_size=no_repeat_ngram_size, hotwords=hotwords, temperature=temperature,
-                compression_ratio_threshold=compression_ratio_threshold, log_prob_threshold=log_prob_threshold,
-                no_speech_threshold=no_speech_threshold, suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
-                without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
-                word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-                append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
-                max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias,
-                language_candidates=language_candidates, multilingual=multilingual, **captions)
+            return self._pipeline()._transcribe(audio, call)
+        sections, in_flight = call.args["sections"], call.args["sections_in_flight"]
         if sections > 1 and not isinstance(audio, np.ndarray):
             audio = self._load_audio(audio)     # (the cuts without VAD are chosen on the samples)
-        features, tokenizer, options, info, speech_chunks = self._prepare_file(
-            audio, language=language, task=task, beam_size=beam_size, best_of=best_of, patience=patience,
-            length_penalty=length_penalty, repetition_penalty=repetition_penalty,
-            no_repeat_ngram_size=no_repeat_ngram_size, temperature=temperature,
-            compression_ratio_threshold=compression_ratio_threshold, log_prob_threshold=log_prob_threshold,
-            no_speech_threshold=no_speech_threshold, condition_on_previous_text=condition_on_previous_text,
-            prompt_reset_on_temperature=prompt_reset_on_temperature, initial_prompt=initial_prompt, prefix=prefix,
-            suppress_blank=suppress_blank, suppress_tokens=suppress_tokens, without_timestamps=without_timestamps,
-            max_initial_timestamp=max_initial_timestamp, word_timestamps=word_timestamps,
-            prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations,
-            multilingual=multilingual, vad_filter=vad_filter, vad_parameters=vad_parameters,
-            max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
-            hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hotwords,
-            language_detection_threshold=language_detection_threshold,
-            language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, captions=captions,
-            language_candidates=language_candidates)
-        options.lockstep_fallback = lockstep_fallback
-        bounds = self._plan_sections(audio, features, speech_chunks, sections) if sections > 1 else None
+        file, tokenizer, options = self._prepare_file(audio, call)
+        bounds = self._plan_sections(audio, file.features, file.speech_chunks, sections) if sections > 1 else None
         if bounds is not None:
             options.section_frames = bounds
         if bounds is not None and len(bounds) > 1:
-            gen = self._generate_sections(features, tokenizer, options, bounds, sections_in_flight or len(bounds))
+            gen = self._generate_sections(file.features, tokenizer, options, bounds, in_flight or len(bounds))
         else:
-            gen = self.generate_segments(features, tokenizer, options)
-        if speech_chunks:
-            from .vad import restore_speech_timestamps
-            gen = restore_speech_timestamps(gen, speech_chunks, SAMPLE_RATE)
-        return _shaped(gen, options), info
+            gen = self.generate_segments(file.features, tokenizer, options)
+        return _finished(gen, file.speech_chunks, options), file.info(options)
 
     def _plan_sections(self, audio: np.ndarray, features: torch.Tensor, speech_chunks, n: int) -> List[Tuple[int, int]]:
         """plan_sections for one prepared file: at the VAD chunk joins when VAD ran, else at the quietest 20 ms frames
@@ -679,72 +809,55 @@ class WhisperModel:
                 torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)), ENERGY_FRAME_MEL * HOP_LENGTH)
         return plan_sections(content, n, energy=energy)
 
-    def _prepare_file(self, audio, *, language, task, beam_size, best_of, patience, length_penalty, repetition_penalty,
-                      no_repeat_ngram_size, temperature, compression_ratio_threshold, log_prob_threshold,
-                      no_speech_threshold, condition_on_previous_text, prompt_reset_on_temperature, initial_prompt,
-                      prefix, suppress_blank, suppress_tokens, without_timestamps, max_initial_timestamp,
-                      word_timestamps, prepend_punctuations, append_punctuations, multilingual, vad_filter,
-                      vad_parameters, max_new_tokens, clip_timestamps, hallucination_silence_threshold, hotwords,
-                      language_detection_threshold, language_detection_segments, sequence_bias=None, captions=None,
-                      language_candidates=()):
-        """What `transcribe` does for one file before its seek loop: load, VAD, log-mel, language, tokenizer, options.
-        captions: _caption_options' dict (the caller has word_timestamps from it already).  language_candidates: the
-        call's argument (the callers pass what they resolved, () when off); in force for a file without a language.
-        -> (features, tokenizer, options, info, speech_chunks)"""
-        candidates = self._language_candidates(language_candidates, language)
+    def _load_file(self, audio, language: Optional[str], vad_filter: bool, vad_parameters, clip_timestamps="0",
+                   language_detection_segments: int = 1, language_detection_threshold: Optional[float] = 0.5,
+                   language_candidates: Optional[Tuple[str, ...]] = None) -> _File:
+        """The sequential path's file: load, VAD-collect, then log-mel of the collected speech, then the language."""
         if not isinstance(audio, np.ndarray):
             audio = self._load_audio(audio)
         audio = np.asarray(audio, dtype=np.float32)
         duration = audio.shape[0] / SAMPLE_RATE
-        duration_after_vad = duration
-        speech_chunks = None
-        vad_opts = None
-        if vad_filter and clip_timestamps in ("0", [0], [0.0]):
+        speech_chunks = vad_opts = None
+        if vad_filter and clip_timestamps in _NO_CLIPS:
             from .vad import collect_chunks, get_speech_timestamps
-            vad_opts = vad_parameters if isinstance(vad_parameters, VadOptions) else VadOptions(**(vad_parameters or {}))
+            vad_opts = _vad_options(vad_parameters)
             speech_chunks = get_speech_timestamps(audio, vad_opts, self)
             audio = collect_chunks(audio, speech_chunks)
-            duration_after_vad = audio.shape[0] / SAMPLE_RATE
-
         with self._lock:
             features = self._features(audio)
-        all_language_probs = None
-        if language is None:
-            if not self.is_multilingual:
-                language, language_probability = "en", 1.0
-            else:
-                language, language_probability, all_language_probs = self.detect_language(
-                    features=features, language_detection_segments=language_detection_segments,
-                    language_detection_threshold=language_detection_threshold or 0.5,
-                    language_candidates=candidates or ())
-        else:
-            if not self.is_multilingual and language != "en":
+        # only this path maps a named non-English language to "en" in an English-only model (and warns); it detects
+        # whatever the VAD left
+        return _File(features, duration, audio.shape[0] / SAMPLE_RATE, vad_opts,
+                     *self._file_language(language, features, language_detection_segments, language_detection_threshold,
+                                          language_candidates, english_only_remap=True), speech_chunks=speech_chunks)
+
+    def _file_language(self, language: Optional[str], features: torch.Tensor, detection_segments: int,
+                       detection_threshold: Optional[float], candidates: Optional[Tuple[str, ...]], *,
+                       english_only_remap: bool = False, detect: bool = True):
+        """Which language a file gets -> (language, probability, all_language_probs, the candidates in force for it).
+        A named language holds (english_only_remap: an English-only model maps another one to "en" and warns);
+        language=None is detected under the call's `candidates`, or is "en" in an English-only model and with
+        detect=False."""
+        if language is not None:
+            if english_only_remap and not self.is_multilingual and language != "en":
                 logger.warning("English-only model used with language=%s; using 'en'", language)
                 language = "en"
-            language_probability = 1.0
-        tokenizer = self.tokenizer(task=task, language=language)
-        temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
-        bias_map, bias_table = self._sequence_bias(tokenizer, sequence_bias)
-        options = TranscriptionOptions(
-            beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
-            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-            log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
-            compression_ratio_threshold=compression_ratio_threshold, condition_on_previous_text=condition_on_previous_text,
-            prompt_reset_on_temperature=prompt_reset_on_temperature, temperatures=temps, initial_prompt=initial_prompt,
-            prefix=prefix, suppress_blank=suppress_blank,
-            suppress_tokens=list(tokenizer.suppressed_tokens(suppress_tokens)) if suppress_tokens else [],
-            without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
-            word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-            append_punctuations=append_punctuations, multilingual=multilingual, max_new_tokens=max_new_tokens,
-            clip_timestamps=clip_timestamps, hallucination_silence_threshold=hallucination_silence_threshold,
-            hotwords=hotwords, sequence_bias=bias_map, sequence_bias_table=bias_table, language_candidates=candidates)
-        if captions and captions["max_line_width"]:
-            options.max_line_width, options.max_line_count = captions["max_line_width"], captions["max_line_count"]
-            options.max_cue_seconds = captions["max_cue_seconds"]
-        info = TranscriptionInfo(language=language, language_probability=language_probability, duration=duration,
-                                 duration_after_vad=duration_after_vad, all_language_probs=all_language_probs,
-                                 transcription_options=options, vad_options=vad_opts)
-        return features, tokenizer, options, info, speech_chunks
+            return language, 1.0, None, None
+        if not (self.is_multilingual and detect):
+            return "en", 1.0, None, candidates
+        return (*self.detect_language(features=features, language_detection_segments=detection_segments,
+                                      language_detection_threshold=detection_threshold or 0.5,
+                                      language_candidates=candidates or ()), candidates)
+
+    def _prepare_file(self, audio, call: _Call, f: int = 0):
+        """What `transcribe` does for file f of a call before its seek loop: load, VAD, log-mel, language, tokenizer,
+        options.  -> (_File, tokenizer, options)"""
+        a = call.args
+        file = self._load_file(audio, a["language"][f], a["vad_filter"], a["vad_parameters"], a["clip_timestamps"],
+                               a["language_detection_segments"], a["language_detection_threshold"],
+                               a["language_candidates"])
+        tokenizer = self.tokenizer(task=a["task"], language=file.language)
+        return file, tokenizer, call.options(self, tokenizer, f, file.language_candidates)
 
     # ------------------------------------------------------------------ prompt / generate
     def get_prompt(self, tokenizer: Tokenizer, previous_tokens: List[int], without_timestamps: bool = False,
@@ -759,18 +872,11 @@ class WhisperModel:
         engine identifies the window and decodes it under that language in the same call (wm_generate_multilingual;
         the prompt holds a placeholder at lang_pos); the result names the language."""
         st = self.dims.specials
-        mit = int(round(options.max_initial_timestamp / self.time_precision))
-        sampling = temperature > 0
         kw = dict(language_auto=self._language_auto(options, [lang_pos])) if lang_pos >= 0 else {}
         res, *lang = self.engine.generate(
-            [slot], [prompt], beam_size=1 if sampling else options.beam_size, patience=options.patience,
-            length_penalty=options.length_penalty, max_length=max_length, temperature=temperature,
-            num_hypotheses=options.best_of if sampling else 1, seed=seed, suppress_tokens=options.suppress_tokens,
-            suppress_blank=options.suppress_blank, max_initial_timestamp_index=mit,
-            with_timestamps=not options.without_timestamps,
-            sot_index=prompt.index(st.sot) if st.sot in prompt else -1, check_every=4,
-            repetition_penalty=options.repetition_penalty, no_repeat_ngram_size=options.no_repeat_ngram_size,
-            sequence_bias=options.sequence_bias_table, **kw)
+            [slot], [prompt], max_length=max_length, num_hypotheses=options.best_of if temperature > 0 else 1,
+            seed=seed, suppress_tokens=options.suppress_tokens,
+            sot_index=prompt.index(st.sot) if st.sot in prompt else -1, **_decode_kwargs(options, temperature), **kw)
         r = res[0]
         return _GenOut(r.tokens, r.score, r.no_speech_prob,
                        st.lang_codes[int(lang[1][0][0])] if lang_pos >= 0 else None)
@@ -832,7 +938,6 @@ class WhisperModel:
         # by levels a round may decode nb windows x best_of rows: reserved once, so no level re-allocates the
         # hypothesis state while the slots are in use
         per = max(opt0.beam_size, opt0.best_of) if levels else (opt0.best_of if sampling else opt0.beam_size)
-        mit = int(round(opt0.max_initial_timestamp / self.time_precision))
         sot = self.dims.specials.sot
         with self._lock:                        # one lock scope per round: the slots hold this round's windows
             self._use_cross_form(opt0.beam_size)      # (a no-op unless another caller changed the form)
@@ -872,15 +977,11 @@ class WhisperModel:
                     if any(p >= 0 for p in pos):
                         first_auto = members[next(j for j, p in enumerate(pos) if p >= 0)]
                         kw["language_auto"] = self._language_auto(batch[first_auto][1].options, pos)
+                    # (the group's suppress list, not opt0's; no `seed`: a sampled pass has its `seeds`)
                     res, *lang = self.engine.generate(
-                        members, prompts, beam_size=1 if t > 0 else opt0.beam_size, patience=opt0.patience,
-                        length_penalty=opt0.length_penalty, max_length=[batch[i][2].max_length for i in members],
-                        temperature=t, suppress_tokens=list(sup),
-                        suppress_blank=opt0.suppress_blank, max_initial_timestamp_index=mit,
-                        with_timestamps=not opt0.without_timestamps,
-                        sot_index=[p.index(sot) if sot in p else -1 for p in prompts], check_every=4,
-                        repetition_penalty=opt0.repetition_penalty, no_repeat_ngram_size=opt0.no_repeat_ngram_size,
-                        sequence_bias=opt0.sequence_bias_table, **kw)
+                        members, prompts, max_length=[batch[i][2].max_length for i in members],
+                        suppress_tokens=list(sup), sot_index=[p.index(sot) if sot in p else -1 for p in prompts],
+                        **_decode_kwargs(opt0, t), **kw)
                     for j, (k, r) in enumerate(zip(ks, res)):
                         out[k] = _GenOut(r.tokens, r.score, r.no_speech_prob)
                         if pos[j] >= 0:
@@ -1005,96 +1106,32 @@ class WhisperModel:
         language_candidates (see `transcribe`): ONE sequence of codes for all files, in force for every file whose
         language is None; a per-file list of lists raises ValueError.
         With throughput mode on, this is BatchedInferencePipeline.transcribe_many."""
-        if hallucination_silence_threshold is not None:
-            raise NotImplementedError(f"hallucination_silence_threshold={hallucination_silence_threshold!r} is not "
-                                      "supported by the MI355X engine")
-        multilingual = self._multilingual(multilingual, language if isinstance(language, (list, tuple)) else [language])
-        if chunk_length not in (None, CHUNK_LENGTH):
-            raise NotImplementedError("chunk_length other than 30 s is not supported")
-        if task not in ("transcribe", "translate"):
-            raise ValueError(f"unknown task {task!r}")
+        args = dict(locals())
         n = len(audios)
-        if max_files < 1:
-            raise ValueError("max_files must be >= 1")
-        if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
-            raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
-        lockstep_fallback = _resolve_lockstep_fallback(lockstep_fallback)
-        captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
-        word_timestamps = captions.pop("word_timestamps", word_timestamps)
-        language_candidates = self._language_candidates(language_candidates) or ()
-
-        def per_file(v, name):
-            if isinstance(v, (list, tuple)):
-                if len(v) != n:
-                    raise ValueError(f"{name}: one value per file expected ({n}), got {len(v)}")
-                return list(v)
-            return [v] * n
-
-        languages, prompts0 = per_file(language, "language"), per_file(initial_prompt, "initial_prompt")
-        hot, prefixes = per_file(hotwords, "hotwords"), per_file(prefix, "prefix")
+        call = _resolve_call(self, "transcribe_many", args, n)
         if self.throughput:
-            if any(p is not None for p in prompts0) or clip_timestamps not in ("0", [0], [0.0]) or \
-                    any(p is not None for p in prefixes):
-                raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
-            if len(set(hot)) > 1:
-                raise NotImplementedError("per-file hotwords in throughput mode")
-            return self._pipeline().transcribe_many(
-                audios, language=language, task=task, beam_size=beam_size, best_of=best_of,
-                patience=patience, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
-                no_repeat_ngram_size=no_repeat_ngram_size, hotwords=hot[0] if n else None, temperature=temperature,
-                compression_ratio_threshold=compression_ratio_threshold, log_prob_threshold=log_prob_threshold,
-                no_speech_threshold=no_speech_threshold, suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
-                without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
-                word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-                append_punctuations=append_punctuations, vad_filter=vad_filter, vad_parameters=vad_parameters,
-                max_new_tokens=max_new_tokens, language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias,
-                language_candidates=language_candidates, multilingual=multilingual, **captions)
-
+            return self._pipeline()._transcribe_many(audios, call)
         files: dict = {}
         results: List[List[Segment]] = [[] for _ in range(n)]
 
         def open_file(f: int) -> SeekState:
             # per file, as `transcribe`: load, VAD, log-mel, language detection (with language=None), options
-            features, tokenizer, options, info, chunks = self._prepare_file(
-                audios[f], language=languages[f], task=task, beam_size=beam_size, best_of=best_of, patience=patience,
-                length_penalty=length_penalty, repetition_penalty=repetition_penalty,
-                no_repeat_ngram_size=no_repeat_ngram_size, temperature=temperature,
-                compression_ratio_threshold=compression_ratio_threshold, log_prob_threshold=log_prob_threshold,
-                no_speech_threshold=no_speech_threshold, condition_on_previous_text=condition_on_previous_text,
-                prompt_reset_on_temperature=prompt_reset_on_temperature, initial_prompt=prompts0[f],
-                prefix=prefixes[f], suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
-                without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
-                word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-                append_punctuations=append_punctuations, multilingual=multilingual, vad_filter=vad_filter,
-                vad_parameters=vad_parameters, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
-                hallucination_silence_threshold=hallucination_silence_threshold, hotwords=hot[f],
-                language_detection_threshold=language_detection_threshold,
-                language_detection_segments=language_detection_segments, sequence_bias=sequence_bias, captions=captions,
-                language_candidates=language_candidates)
-            options.lockstep_fallback = lockstep_fallback
-            files[f] = [features, info, chunks]
-            return SeekState(features.shape[1] - 1, tokenizer, options, self.max_length, self.frames_per_second)
+            file, tokenizer, options = self._prepare_file(audios[f], call, f)
+            files[f] = (file, options)
+            return SeekState(file.features.shape[1] - 1, tokenizer, options, self.max_length, self.frames_per_second)
 
         reserved = [0]
 
         def decode_round(batch):
             self._lockstep_round(batch, reserved, lambda f, out: results[f].extend(self._segment(d) for d in out),
-                                 features_of=lambda f: files[f][0])
+                                 features_of=lambda f: files[f][0].features)
 
         def close_file(f: int) -> None:
-            files[f][0] = None                      # the file's log-mel leaves the device with its last window
+            files[f][0].features = None             # the file's log-mel leaves the device with its last window
 
         run_lockstep(n, max_files, open_file, decode_round, close_file)
-        out = []
-        for f in range(n):
-            _, info, chunks = files[f]
-            segments = results[f]
-            if chunks:
-                from .vad import restore_speech_timestamps
-                segments = list(restore_speech_timestamps(iter(segments), chunks, SAMPLE_RATE))
-            out.append((list(_shaped(iter(segments), info.transcription_options)), info))
-        return out
+        return [(list(_finished(iter(results[f]), file.speech_chunks, options)), file.info(options))
+                for f, (file, options) in sorted(files.items())]
 
     # ------------------------------------------------------------------ forced alignment
     def align(self, audio: Union[str, BinaryIO, np.ndarray], text: Union[str, Sequence[str]],
@@ -1124,16 +1161,8 @@ class WhisperModel:
         if not fa.split_lines(text):
             raise ValueError("align: empty text")
         with self._lock:
-            features, tokenizer, options, tinfo, speech_chunks = self._prepare_file(
-                audio, language=language, task=task, beam_size=1, best_of=1, patience=1, length_penalty=1,
-                repetition_penalty=1, no_repeat_ngram_size=0, temperature=0.0, compression_ratio_threshold=None,
-                log_prob_threshold=None, no_speech_threshold=None, condition_on_previous_text=False,
-                prompt_reset_on_temperature=0.5, initial_prompt=None, prefix=None, suppress_blank=True,
-                suppress_tokens=[-1], without_timestamps=True, max_initial_timestamp=1.0, word_timestamps=True,
-                prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations, multilingual=False,
-                vad_filter=vad_filter, vad_parameters=vad_parameters, max_new_tokens=None, clip_timestamps="0",
-                hallucination_silence_threshold=None, hotwords=None, language_detection_threshold=0.5,
-                language_detection_segments=1)
+            file = self._load_file(audio, language, vad_filter, vad_parameters)
+            features, tokenizer = file.features, self.tokenizer(task=task, language=file.language)
             heads = self.dims.default_alignment_heads()
             self._use_cross_form(1)             # one teacher-forced row set per window, as a greedy decode's alignment
 
@@ -1142,15 +1171,12 @@ class WhisperModel:
                 return self.engine.align_open_batch([0], tokenizer.sot_sequence, [tokens], [size], heads,
                                                     median_filter_width)[0]
 
-            out, stats = fa.forced_align(tokenizer, text, features.shape[1] - 1, tinfo.duration_after_vad, align_window,
+            out, stats = fa.forced_align(tokenizer, text, features.shape[1] - 1, file.duration_after_vad, align_window,
                                          max_window_tokens, max_cue_chars, prepend_punctuations, append_punctuations,
                                          self.frames_per_second, self.tokens_per_second)
-        segments = [self._segment(d) for d in out]
-        if speech_chunks:
-            from .vad import restore_speech_timestamps
-            segments = list(restore_speech_timestamps(iter(segments), speech_chunks, SAMPLE_RATE))
-        info = AlignmentInfo(language=tinfo.language, language_probability=tinfo.language_probability,
-                             duration=tinfo.duration, duration_after_vad=tinfo.duration_after_vad,
+        segments = list(_finished((self._segment(d) for d in out), file.speech_chunks))
+        info = AlignmentInfo(language=file.language, language_probability=file.language_probability,
+                             duration=file.duration, duration_after_vad=file.duration_after_vad,
                              windows=stats["windows"], unaligned_words=stats["unaligned_words"],
                              window_rows=stats["window_rows"])
         return segments, info
@@ -1345,7 +1371,6 @@ class BatchedInferencePipeline:
         # one prompt for every window (wm_generate takes one prompt length): hotwords fit, a prefix does not
         prompt = m.get_prompt(tokenizer, ip, options.without_timestamps, hotwords=options.hotwords)
         max_length = min(m.max_length, len(prompt) + options.max_new_tokens) if options.max_new_tokens else m.max_length
-        mit = int(round(options.max_initial_timestamp / m.time_precision))
         per = max(options.beam_size, options.best_of, 1)
         # cross-attention form per batch (WhisperModel._use_cross_form), chosen for the FIRST pass: greedy
         # (beam 1) decodes one row per window -> factored; beam groups -> projected (large-v3, 150 windows, beam 5
@@ -1354,14 +1379,14 @@ class BatchedInferencePipeline:
         prev_form = eng.option("cross_mode")
         try:
             return self._decode_batches(features, windows, time_offsets, tokenizer, options, seed, files, seek_bases,
-                                        last_speech, prompt, max_length, mit, per, auto_form)
+                                        last_speech, prompt, max_length, per, auto_form)
         finally:
             if auto_form:                      # leave the engine in the form the caller had configured
                 with m._lock:
                     eng.set_option("cross_mode", 1 if prev_form is None else prev_form)
 
     def _decode_batches(self, features, windows, time_offsets, tokenizer, options, seed, files, seek_bases,
-                        last_speech, prompt, max_length, mit, per, auto_form) -> List[WindowResult]:
+                        last_speech, prompt, max_length, per, auto_form) -> List[WindowResult]:
         m = self.model
         eng = m.engine
         st = m.dims.specials
@@ -1388,7 +1413,6 @@ class BatchedInferencePipeline:
                 for ti, T in enumerate(options.temperatures):
                     if not pending:
                         break
-                    sampling = T > 0
                     prompts = [prompt] * len(pending)
                     kw = {}
                     if auto and ti == 0:
@@ -1397,15 +1421,9 @@ class BatchedInferencePipeline:
                         prompts = [prompt[:lang_pos] + [tokenizer.for_language(win_lang[i]).language] +
                                    prompt[lang_pos + 1:] for i in pending]
                     res, *lang = eng.generate(
-                        pending, prompts, beam_size=1 if sampling else options.beam_size,
-                        patience=options.patience, length_penalty=options.length_penalty, max_length=max_length,
-                        temperature=T, num_hypotheses=options.best_of if sampling else 1, seed=seed + 7919 * ti + b0,
-                        suppress_tokens=options.suppress_tokens, suppress_blank=options.suppress_blank,
-                        max_initial_timestamp_index=mit, with_timestamps=not options.without_timestamps,
-                        sot_index=prompt.index(st.sot), check_every=4, compact=self.compact,
-                        repetition_penalty=options.repetition_penalty,
-                        no_repeat_ngram_size=options.no_repeat_ngram_size,
-                        sequence_bias=options.sequence_bias_table, **kw)
+                        pending, prompts, max_length=max_length, num_hypotheses=options.best_of if T > 0 else 1,
+                        seed=seed + 7919 * ti + b0, suppress_tokens=options.suppress_tokens,
+                        sot_index=prompt.index(st.sot), compact=self.compact, **_decode_kwargs(options, T), **kw)
                     if auto and ti == 0:
                         win_lang = {i: st.lang_codes[int(t)] for i, t in zip(pending, lang[1][0])}
                     still = []
@@ -1486,33 +1504,17 @@ class BatchedInferencePipeline:
         language_candidates: as WhisperModel.transcribe (the whitelist of the file's language detection).
         max_line_width, max_line_count, max_cue_seconds: caption shaping as in WhisperModel.transcribe; the windows
         then decode as with word_timestamps=True and the segments leave through captions.shape_captions."""
-        if hallucination_silence_threshold is not None:
-            raise NotImplementedError(f"hallucination_silence_threshold={hallucination_silence_threshold!r} is not "
-                                      "supported by the MI355X engine")
-        multilingual = self.model._multilingual(multilingual, [language])
-        if prefix is not None:       # every window of a batch shares one prompt length; a prefix belongs to the first only
-            raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
-        captions = _caption_options(max_line_width, max_line_count, max_cue_seconds)
-        word_timestamps = captions.pop("word_timestamps", word_timestamps)
-        language_candidates = self.model._language_candidates(language_candidates, language) or ()
-        prep = self._prepare(audio, language, vad_filter, vad_parameters, language_detection_segments,
-                             language_detection_threshold, language_candidates)
-        tokenizer = self.model.tokenizer(task=task, language=prep["language"])
-        options = self._options(
-            tokenizer, beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
-            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, hotwords=hotwords,
-            temperature=temperature, compression_ratio_threshold=compression_ratio_threshold,
-            log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
-            initial_prompt=initial_prompt, suppress_blank=suppress_blank, suppress_tokens=suppress_tokens,
-            without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
-            word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-            append_punctuations=append_punctuations, max_new_tokens=max_new_tokens, clip_timestamps=clip_timestamps,
-            sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias), captions=captions,
-            language_candidates=prep["language_candidates"], multilingual=multilingual)
-        windows = prep["windows"]
-        offsets = [s * HOP_LENGTH / SAMPLE_RATE for s, _ in windows]
-        results = self.decode_windows(prep["features"], windows, offsets, tokenizer, options, last_speech={})
-        return self._segments(prep["features"], results, tokenizer, options), self._info(prep, options)
+        args = dict(locals())
+        return self._transcribe(audio, _resolve_call(self.model, "batched", args))
+
+    def _transcribe(self, audio, call: _Call):
+        """`transcribe` for a resolved call: the public method's, or WhisperModel.transcribe's in throughput mode."""
+        file = self._prepare(audio, call)
+        tokenizer = self.model.tokenizer(task=call.args["task"], language=file.language)
+        options = call.options(self.model, tokenizer, 0, file.language_candidates)
+        offsets = [s * HOP_LENGTH / SAMPLE_RATE for s, _ in file.windows]
+        results = self.decode_windows(file.features, file.windows, offsets, tokenizer, options, last_speech={})
+        return self._segments(results, tokenizer, options), file.info(options)
 
     def transcribe_many(self, audios: Sequence[Union[str, BinaryIO, np.ndarray]],
                         language: Union[None, str, Sequence[Optional[str]]] = None, task: str = "transcribe",
@@ -1528,60 +1530,49 @@ class BatchedInferencePipeline:
         mapping for all files; a per-file list raises ValueError.  max_line_width, max_line_count, max_cue_seconds
         (in **kw too): caption shaping as in WhisperModel.transcribe, applied to every file's segments on their own.
         language_candidates (in **kw): one sequence of codes for all files, as WhisperModel.transcribe_many."""
-        n = len(audios)
-        if kw.pop("prefix", None) is not None:
-            raise NotImplementedError("initial_prompt / clip_timestamps / prefix in throughput mode")
-        captions = _caption_options(kw.pop("max_line_width", None), kw.pop("max_line_count", None),
-                                    kw.pop("max_cue_seconds", None))
-        if "word_timestamps" in captions:
-            kw["word_timestamps"] = captions.pop("word_timestamps")
-        sequence_bias = kw.pop("sequence_bias", None)
-        if sequence_bias is not None and not isinstance(sequence_bias, Mapping):
-            raise ValueError("sequence_bias: one mapping for all files expected, not a per-file list")
-        language_candidates = self.model._language_candidates(kw.pop("language_candidates", None)) or ()
-        kw["multilingual"] = self.model._multilingual(kw.pop("multilingual", None),
-                                                      language if isinstance(language, (list, tuple)) else [language])
-        langs = list(language) if isinstance(language, (list, tuple)) else [language] * n
-        if len(langs) != n:
-            raise ValueError("one language per file")
-        preps = [self._prepare(a, l, vad_filter, vad_parameters, language_detection_segments,
-                               language_detection_threshold, language_candidates) for a, l in zip(audios, langs)]
-        out: List[Optional[tuple]] = [None] * n
+        args = dict(locals())
+        unknown = [k for k in kw if k not in _BATCHED_DEFAULTS]
+        if unknown:
+            raise TypeError(f"transcribe_many() got an unexpected keyword argument {unknown[0]!r}")
+        args.update(_BATCHED_DEFAULTS, **kw)     # **kw: the options of `transcribe`, with their defaults there
+        return self._transcribe_many(audios, _resolve_call(self.model, "batched_many", args, len(audios)))
+
+    def _transcribe_many(self, audios, call: _Call):
+        """`transcribe_many` for a resolved call: the public method's, or WhisperModel.transcribe_many's in throughput
+        mode."""
+        preps = [self._prepare(a, call, f) for f, a in enumerate(audios)]
+        out: List[Optional[tuple]] = [None] * len(audios)
         last_speech: dict = {}
-        for lang in sorted({p["language"] for p in preps}):
-            files = [i for i, p in enumerate(preps) if p["language"] == lang]
-            tokenizer = self.model.tokenizer(task=task, language=lang)
-            options = self._options(tokenizer, sequence_bias=self.model._sequence_bias(tokenizer, sequence_bias),
-                                    captions=captions, **kw)
+        for lang in sorted({p.language for p in preps}):
+            files = [i for i, p in enumerate(preps) if p.language == lang]
+            tokenizer = self.model.tokenizer(task=call.args["task"], language=lang)
             # (the options are one object per language group: they echo the call's whitelist when any file of the
             # group had its language detected under it)
-            options.language_candidates = next((preps[i]["language_candidates"] for i in files
-                                                if preps[i]["language_candidates"]), None)
-            feats = torch.cat([preps[i]["features"] for i in files], dim=1) if len(files) > 1 else preps[files[0]]["features"]
+            options = call.options(self.model, tokenizer, files[0], next(
+                (preps[i].language_candidates for i in files if preps[i].language_candidates), None))
+            feats = torch.cat([preps[i].features for i in files], dim=1) if len(files) > 1 else preps[files[0]].features
             windows, offsets, fids, bases = [], [], [], {}
             base = 0
             for i in files:
                 bases[i] = base
-                for s, nf in preps[i]["windows"]:
+                for s, nf in preps[i].windows:
                     windows.append((base + s, nf))
                     offsets.append(s * HOP_LENGTH / SAMPLE_RATE)
                     fids.append(i)
-                base += preps[i]["features"].shape[1]
+                base += preps[i].features.shape[1]
             results = self.decode_windows(feats, windows, offsets, tokenizer, options, files=fids,
                                           seek_bases=[bases[f] for f in fids], last_speech=last_speech)
             for i in files:
                 mine = [wr for wr, f in zip(results, fids) if f == i]
-                out[i] = (list(self._segments(None, mine, tokenizer, options)), self._info(preps[i], options))
+                out[i] = (list(self._segments(mine, tokenizer, options)), preps[i].info(options))
         return out
 
-    def _prepare(self, audio, language, vad_filter, vad_parameters, language_detection_segments,
-                 language_detection_threshold, language_candidates=()) -> dict:
-        """One file: PCM, log-mel, its windows (VAD-bounded or fixed) and its language.  `audio` may be an
-        IngestResult (vlog_amd/ingest.py: PCM and log-mel already on the device, computed while streaming).
-        language_candidates: the call's resolved whitelist (() = off), in force when the file has no language."""
+    def _prepare(self, audio, call: _Call, f: int = 0) -> _File:
+        """The throughput path's file: PCM, then log-mel of the WHOLE file, then its windows (VAD-bounded or fixed) and
+        its language.  `audio` may be an IngestResult (vlog_amd/ingest.py: PCM and log-mel already on the device,
+        computed while streaming)."""
         from .ingest import IngestResult
-        m = self.model
-        candidates = m._language_candidates(language_candidates, language)
+        m, a = self.model, call.args
         if isinstance(audio, IngestResult):
             features, duration = audio.features, audio.duration
             audio = audio.pcm
@@ -1594,71 +1585,23 @@ class BatchedInferencePipeline:
                 features = m._features(audio)
         content = features.shape[1] - 1
         vad_opts = None
-        if vad_filter:
+        if a["vad_filter"]:
             from .vad import get_speech_timestamps
-            vad_opts = vad_parameters if isinstance(vad_parameters, VadOptions) else VadOptions(**(vad_parameters or {}))
+            vad_opts = _vad_options(a["vad_parameters"])
             chunks = get_speech_timestamps(audio, vad_opts, m)
             windows = self.vad_windows(chunks, content)
             duration_after_vad = sum(c["end"] - c["start"] for c in chunks) / SAMPLE_RATE
         else:
             windows = self.fixed_windows(content)
             duration_after_vad = duration
-        all_language_probs = None
-        if language is None:
-            if m.is_multilingual and windows:
-                language, language_probability, all_language_probs = m.detect_language(
-                    features=features, language_detection_segments=language_detection_segments,
-                    language_detection_threshold=language_detection_threshold or 0.5,
-                    language_candidates=candidates or ())
-            else:
-                language, language_probability = "en", 1.0
-        else:
-            language_probability = 1.0
-        return dict(features=features, windows=windows, duration=duration, duration_after_vad=duration_after_vad,
-                    vad_opts=vad_opts, language=language, language_probability=language_probability,
-                    all_language_probs=all_language_probs, language_candidates=candidates)
+        # only this path skips the detection for a file with no windows; it keeps a named language as it is, in an
+        # English-only model too
+        return _File(features, duration, duration_after_vad, vad_opts,
+                     *m._file_language(a["language"][f], features, a["language_detection_segments"],
+                                       a["language_detection_threshold"], a["language_candidates"],
+                                       detect=bool(windows)), windows=windows)
 
-    @staticmethod
-    def _options(tokenizer: Tokenizer, beam_size: int = 5, best_of: int = 5, patience: float = 1,
-                 length_penalty: float = 1, temperature=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
-                 compression_ratio_threshold: Optional[float] = 2.4, log_prob_threshold: Optional[float] = -1.0,
-                 no_speech_threshold: Optional[float] = 0.6, initial_prompt=None, suppress_blank: bool = True,
-                 suppress_tokens: Optional[List[int]] = [-1], without_timestamps: bool = True,
-                 max_initial_timestamp: float = 1.0, word_timestamps: bool = False,
-                 prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
-                 max_new_tokens: Optional[int] = None, clip_timestamps=None, repetition_penalty: float = 1,
-                 no_repeat_ngram_size: int = 0, hotwords: Optional[str] = None,
-                 sequence_bias=(None, None), captions: Optional[dict] = None,
-                 language_candidates: Optional[Tuple[str, ...]] = None,
-                 multilingual: bool = False) -> TranscriptionOptions:
-        """sequence_bias: (the mapping in force, the engine's table), WhisperModel._sequence_bias' pair; captions:
-        _caption_options' dict (word_timestamps is the caller's, set from it already)"""
-        on = captions if captions and captions["max_line_width"] else {}
-        temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
-        return TranscriptionOptions(
-            beam_size=beam_size, best_of=best_of, patience=patience, length_penalty=length_penalty,
-            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-            log_prob_threshold=log_prob_threshold, no_speech_threshold=no_speech_threshold,
-            compression_ratio_threshold=compression_ratio_threshold, condition_on_previous_text=False,
-            prompt_reset_on_temperature=0.5, temperatures=temps, initial_prompt=initial_prompt, prefix=None,
-            suppress_blank=suppress_blank,
-            suppress_tokens=list(tokenizer.suppressed_tokens(suppress_tokens)) if suppress_tokens else [],
-            without_timestamps=without_timestamps, max_initial_timestamp=max_initial_timestamp,
-            word_timestamps=word_timestamps, prepend_punctuations=prepend_punctuations,
-            append_punctuations=append_punctuations, multilingual=bool(multilingual), max_new_tokens=max_new_tokens,
-            clip_timestamps=clip_timestamps or "0", hallucination_silence_threshold=None, hotwords=hotwords,
-            sequence_bias=sequence_bias[0], sequence_bias_table=sequence_bias[1],
-            max_line_width=on.get("max_line_width"), max_line_count=on.get("max_line_count"),
-            max_cue_seconds=on.get("max_cue_seconds"), language_candidates=language_candidates or None)
-
-    @staticmethod
-    def _info(prep: dict, options: TranscriptionOptions) -> TranscriptionInfo:
-        return TranscriptionInfo(language=prep["language"], language_probability=prep["language_probability"],
-                                 duration=prep["duration"], duration_after_vad=prep["duration_after_vad"],
-                                 all_language_probs=prep["all_language_probs"], transcription_options=options,
-                                 vad_options=prep["vad_opts"])
-
-    def _segments(self, features, results: List[WindowResult], tokenizer: Tokenizer, options: TranscriptionOptions):
+    def _segments(self, results: List[WindowResult], tokenizer: Tokenizer, options: TranscriptionOptions):
         """The windows' segments in order, ids 1, 2, ...; through captions.shape_captions when the options have it on."""
         return _shaped(self._window_stream(results, tokenizer, options), options)
 
@@ -1678,15 +1621,28 @@ class BatchedInferencePipeline:
                               language=wr.language)
 
 
+def _defaults(fn) -> dict:
+    return {p.name: p.default for p in inspect.signature(fn).parameters.values() if p.default is not p.empty}
+
+
+# The one table of defaults is the public signatures themselves, read once: WhisperModel.transcribe's for
+# default_batched_options, and for the **kw of BatchedInferencePipeline.transcribe_many the arguments of its
+# `transcribe` that it neither names itself nor has ever taken (the four that `transcribe` accepts and ignores or
+# refuses; in **kw they are a TypeError, as every unknown name).
+_SEQUENTIAL_DEFAULTS = _defaults(WhisperModel.transcribe)
+_BATCHED_DEFAULTS = {k: v for k, v in _defaults(BatchedInferencePipeline.transcribe).items()
+                     if k not in _defaults(BatchedInferencePipeline.transcribe_many)
+                     and k not in ("log_progress", "chunk_length", "hallucination_silence_threshold", "batch_size")}
+
+
 def default_batched_options(**kw) -> dict:
     """TranscriptionOptions fields (as a dict) for the batched/sharded throughput mode."""
-    base = dict(beam_size=5, best_of=5, patience=1.0, length_penalty=1.0, repetition_penalty=1.0,
-                no_repeat_ngram_size=0, log_prob_threshold=-1.0, no_speech_threshold=0.6,
-                compression_ratio_threshold=2.4, condition_on_previous_text=False, prompt_reset_on_temperature=0.5,
-                temperatures=[0.0, 0.2, 0.4, 0.6, 0.8, 1.0], initial_prompt=None, prefix=None, suppress_blank=True,
-                suppress_tokens=[-1], without_timestamps=False, max_initial_timestamp=1.0, word_timestamps=False,
-                prepend_punctuations="\"'“¿([{-", append_punctuations="\"'.。,，!！?？:：”)]}、", multilingual=False,
-                max_new_tokens=None, clip_timestamps="0", hallucination_silence_threshold=None, hotwords=None)
+    base = {fd.name: _SEQUENTIAL_DEFAULTS[fd.name] for fd in fields(TranscriptionOptions)
+            if fd.default is MISSING and fd.name != "temperatures"}            # the fields without a default
+    base.update({fd.name: float(base[fd.name]) for fd in fields(TranscriptionOptions)
+                 if fd.type == "float" and fd.name in base})                   # (the signatures write 1 for 1.0)
+    base.update(condition_on_previous_text=False, temperatures=list(_SEQUENTIAL_DEFAULTS["temperature"]),
+                suppress_tokens=[-1], multilingual=False)
     if "temperature" in kw:
         t = kw.pop("temperature")
         kw["temperatures"] = list(t) if isinstance(t, (list, tuple)) else [t]
